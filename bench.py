@@ -17,6 +17,12 @@ Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W          # N=1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N ...      # N>1, one rank/GPU
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, print the one JSON result line. --dump-outputs DIR
+additionally writes the last timed step's outputs as .npy files (inputs are
+seeded, so two builds can be compared output for output); --full is the
+switch for extended measurements beyond the headline (none today).
 """
 
 import argparse
@@ -135,7 +141,67 @@ def parse_args():
         choices=["auto", "device", "host", "none"],
         help="auto: dataset HBM-resident after first read",
     )
+    p.add_argument(
+        "--seed",
+        type=int,
+        default=0,
+        help="seeds the per-epoch shuffles and the model init, so the same "
+        "arguments give the same inputs on every run",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        type=str,
+        default=None,
+        metavar="DIR",
+        help="after the timed steps, write what the LAST timed step "
+        "computed (loss, gradients, updated parameters, plus the batch it "
+        "consumed) to DIR/<name>.npy as float32, so two builds can be "
+        "compared output for output (rank 0 only; large arrays are a "
+        "fixed seeded row sample)",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the extended measurements that the headline figure "
+        "does not need. A plain run is setup, warmup, the timed steps and "
+        "the result line only; any future extra measurement (baselines, "
+        "other precisions or sizes, per-kernel figures) belongs behind "
+        "this switch. There are none yet: today's extras are separate "
+        "invocations (--dtype fp32, RSDL_* knobs, tools/)",
+    )
     return p.parse_args()
+
+
+# --dump-outputs budget: at most this many elements per array (float32),
+# which keeps a full dump (two sampled [rows, cols] arrays + ~0.4M params
+# and grads) far below 64 MB.
+_DUMP_MAX_ELEMS = 2_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each named tensor as out_dir/<name>.npy (float32). An array
+    over the element budget keeps a fixed, seeded, sorted sample of its
+    rows (the same rows on every run and every build)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        if t.numel() > _DUMP_MAX_ELEMS:
+            row_elems = max(1, t.numel() // t.shape[0])
+            keep = max(1, _DUMP_MAX_ELEMS // row_elems)
+            rows = np.sort(
+                np.random.default_rng(0).choice(
+                    t.shape[0], size=keep, replace=False
+                )
+            )
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(
+            os.path.join(out_dir, name.replace(".", "_") + ".npy"),
+            t.to(torch.float32).cpu().numpy(),
+        )
 
 
 def main():
@@ -239,7 +305,11 @@ def main():
         device=device,
         source_cache=args.source_cache,
         output=args.loader_output,
+        seed=args.seed,
     )
+    # Same arguments -> same initial weights (the shuffles are seeded
+    # through the engine above, the synthetic data by its row indices).
+    torch.manual_seed(args.seed)
 
     # Default train step: the fused chain-kernel path (fwd+loss+bwd in two
     # hand-written MFMA kernels + split-K wgrads — measured faster than
@@ -325,6 +395,12 @@ def main():
             torch.distributed.all_reduce(sl, async_op=True)
         )
 
+    # --dump-outputs: every step leaves references (no copies, no syncs)
+    # to the batch it consumed and the loss it computed; after the timed
+    # loop these are the last timed step's. None on a run without the
+    # option, which then does nothing extra per step.
+    last_out = {} if args.dump_outputs else None
+
     def one_step():
         t_wait0 = time.perf_counter()
         cur_epoch[0], (data, target) = next(it)
@@ -336,15 +412,17 @@ def main():
         if use_fused:
             if overlap_ar:
                 ar_works.clear()
-                fused_step(model, x, target, grad_hook=_overlap_hook)
+                loss = fused_step(model, x, target, grad_hook=_overlap_hook)
                 for w in ar_works:
                     w.wait()
             else:
-                fused_step(model, x, target)
+                loss = fused_step(model, x, target)
                 if flat_grad is not None:
                     flat_grad.div_(world)
                     torch.distributed.all_reduce(flat_grad)
             opt.step()
+            if last_out is not None:
+                last_out.update(x=x, target=target, loss=loss)
             return wait
         opt.zero_grad(set_to_none=True)
         with amp():
@@ -352,6 +430,8 @@ def main():
             loss = loss_fn(out.float(), target)
         loss.backward()
         opt.step()
+        if last_out is not None:
+            last_out.update(x=x, target=target, loss=loss)
         return wait
 
     # RSDL_HIP_GRAPH=1 (world 1, CUDA, fixed batch shape): capture the
@@ -406,6 +486,10 @@ def main():
         graph_state["sx"].copy_(x, non_blocking=True)
         graph_state["st"].copy_(target, non_blocking=True)
         graph_state["g"].replay()
+        if last_out is not None:
+            # The captured step keeps its loss inside the graph; the
+            # batch, gradients and parameters are still dumped.
+            last_out.update(x=x, target=target, loss=None)
         return wait
 
     if use_graph:
@@ -544,6 +628,24 @@ def main():
         )
         elapsed = float(t.cpu().item())
 
+    # What the last timed step handed its caller: the loss, every
+    # parameter's gradient and the parameters after the optimizer step
+    # (plus the batch it consumed, to tell an input mismatch from a
+    # compute mismatch). Nothing below touches the model again.
+    if last_out and rank == 0:
+        arrays = {
+            "batch_features": last_out["x"],
+            "batch_target": last_out["target"],
+        }
+        if last_out["loss"] is not None:
+            arrays["loss"] = last_out["loss"]
+        for name, p in model.named_parameters():
+            arrays[f"param.{name}"] = p
+            if p.grad is not None:
+                arrays[f"grad.{name}"] = p.grad
+        dump_outputs(args.dump_outputs, arrays)
+    last_out = None
+
     # Drain the remaining epochs so engine threads/collectives finish clean.
     drained = 0
     try:
@@ -592,6 +694,7 @@ def main():
                 "num_reducers": args.reducers_per_gpu * world,
                 "max_concurrent_epochs": args.max_concurrent_epochs,
                 "parallelism": f"dp{n_gpus}",
+                "seed": args.seed,
                 # Proof the timed region crossed >= 1 epoch boundary, i.e.
                 # the number includes a full per-epoch reshuffle: untimed
                 # positioning steps burned after warmup, and the count of

@@ -706,7 +706,10 @@ at::Tensor wgrad_frag_bf16(const at::Tensor& AT, const at::Tensor& BT,
               "wgrad_frag: AT numel mismatch");
   TORCH_CHECK(BT.numel() == (K / 32) * mchunks * 512,
               "wgrad_frag: BT numel mismatch");
-  TORCH_CHECK((nt_w == 2 && kt_w == 4) || (nt_w == 1 && kt_w == 8),
+  // Must list every config launch_wgrad_frag dispatches (an unlisted one
+  // would fall through its if-chain and leave the partials unwritten).
+  TORCH_CHECK((nt_w == 2 && kt_w == 4) || (nt_w == 1 && kt_w == 8) ||
+                  (nt_w == 1 && kt_w == 4),
               "wgrad_frag: unsupported tile config");
   TORCH_CHECK(N % (nt_w * 128) == 0 && K % (kt_w * 32) == 0,
               "wgrad_frag: N/K not divisible by block shape");

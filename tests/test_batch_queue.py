@@ -422,12 +422,29 @@ def test_custom_queue_placement(tmp_path, monkeypatch):
     """The reference's test_custom_resources pins the queue ACTOR to a node
     via Ray resources; our placement control is the rendezvous directory
     (RSDL_QUEUE_DIR) for the named-socket server. Verify the socket lands
-    in the requested dir and a client connects through it."""
-    monkeypatch.setenv("RSDL_QUEUE_DIR", str(tmp_path))
+    in the requested dir and a client connects through it.
+
+    The directory is a fresh one directly under the shortest writable temp
+    root rather than pytest's tmp_path: an AF_UNIX socket path is limited
+    to ~107 bytes, which a deeply nested tmp_path (long TMPDIR + per-user +
+    per-test levels) overflows before the queue code is ever reached."""
     import os
+    import shutil
+    import tempfile
+
+    roots = [
+        d for d in (tempfile.gettempdir(), "/tmp")
+        if os.path.isdir(d) and os.access(d, os.W_OK)
+    ]
+    tmp_path = tempfile.mkdtemp(prefix="rq", dir=min(roots, key=len))
+    monkeypatch.setenv("RSDL_QUEUE_DIR", tmp_path)
 
     name = "placed_queue"
-    q = BatchQueue(1, 1, 1, name=name)
+    try:
+        q = BatchQueue(1, 1, 1, name=name)
+    except BaseException:
+        shutil.rmtree(tmp_path, ignore_errors=True)
+        raise
     try:
         socks = [
             os.path.join(root, f)
@@ -448,6 +465,7 @@ def test_custom_queue_placement(tmp_path, monkeypatch):
         assert q.get(0, 0, timeout=10) == 42
     finally:
         q.shutdown()
+        shutil.rmtree(tmp_path, ignore_errors=True)
 
 
 def test_queue_concurrent_stress():

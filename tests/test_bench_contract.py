@@ -44,6 +44,96 @@ def test_bench_stdout_is_one_json_line(tmp_path):
     assert d["higher_is_better"] is True and d["scaling"] == "weak"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy
+    files; with the same arguments two runs consume the identical batch
+    (seeded shuffle + seeded model init) and so compute the same outputs.
+    The second run adds --full, which must leave the plain run's result
+    line and outputs as they are."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env["RSDL_TUNABLEOP"] = "0"
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / f"dump_{tag}"
+        proc = subprocess.run(
+            [
+                sys.executable,
+                os.path.join(REPO, "bench.py"),
+                "--gpus", "1", "--steps", "3", "--warmup", "1",
+                "--rows-per-gpu", "120000", "--batch-size", "30000",
+                "--num-cols", "8", "--files-per-gpu", "2",
+                "--reducers-per-gpu", "2", "--device", "cpu",
+                "--dtype", "fp32", "--data-dir", str(tmp_path / "data"),
+                "--dump-outputs", str(out),
+            ] + extra,
+            capture_output=True,
+            text=True,
+            timeout=300,
+            env=env,
+            cwd=REPO,
+        )
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, f"stdout must be one JSON line, got: {lines}"
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        dumps.append(
+            {p.name: np.load(p) for p in sorted(out.glob("*.npy"))}
+        )
+    a, b = dumps
+    assert set(a) == set(b)
+    assert {"batch_features.npy", "batch_target.npy", "loss.npy"} <= set(a)
+    assert any(n.startswith("grad_") for n in a)
+    assert any(n.startswith("param_") for n in a)
+    assert a["batch_features.npy"].shape == (30000, 8)
+    total = 0
+    for name in a:
+        assert a[name].dtype == np.float32, name
+        assert np.isfinite(a[name]).all(), name
+        total += a[name].nbytes
+    assert total <= 64 * 2**20
+    # Inputs are bit-identical; outputs match to fp32 reduction-order noise.
+    np.testing.assert_array_equal(
+        a["batch_features.npy"], b["batch_features.npy"]
+    )
+    np.testing.assert_array_equal(
+        a["batch_target.npy"], b["batch_target.npy"]
+    )
+    for name in a:
+        np.testing.assert_allclose(
+            a[name], b[name], rtol=1e-5, atol=1e-7, err_msg=name
+        )
+
+
+def test_bench_dump_samples_large_arrays(tmp_path):
+    """An array over the element budget is dumped as a fixed seeded row
+    sample: same rows on every call, taken in order from the source."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    rows = bench._DUMP_MAX_ELEMS // 4 + 1000
+    big = torch.arange(rows * 4, dtype=torch.float32).reshape(rows, 4)
+    small = torch.tensor(3.5, dtype=torch.float64)
+    for tag in ("a", "b"):
+        bench.dump_outputs(
+            str(tmp_path / tag), {"big.one": big, "small": small}
+        )
+    a = np.load(tmp_path / "a" / "big_one.npy")
+    b = np.load(tmp_path / "b" / "big_one.npy")
+    assert a.dtype == np.float32 and a.shape == (bench._DUMP_MAX_ELEMS // 4, 4)
+    np.testing.assert_array_equal(a, b)
+    # rows are whole source rows, in increasing order
+    assert (np.diff(a[:, 0]) > 0).all()
+    np.testing.assert_array_equal(a[:, 1], a[:, 0] + 1)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.tolist() == [3.5]
+
+
 def test_bench_world2_gloo(tmp_path):
     """The driver's SCALE tier launches bench.py under torchrun with N>1.
     Exercise that exact path at world 2 on CPU/gloo: per-rank stripe
