@@ -542,4 +542,500 @@ void launch_pack_columns(
                      table, num_cols, n_rows);
 }
 
+// ---------------------------------------------------------------------------
+// Feature standardization (opt-in, ShuffleEngine(normalize=...)).
+//
+//   * column_stats_kernel   — the FIT: one read-only pass over the packed
+//                             source block, per-element (count, Σ(x-p),
+//                             Σ(x-p)²) in fp64 about a pivot p (the first
+//                             finite value of the element, row 0 as a rule).
+//   * unpack_permute_affine — the APPLY: the fused unpack with
+//                             y = cast((float)((double(x) - shift) * scale))
+//                             evaluated in fp64 BEFORE the narrowing cast.
+//
+// The fit must be bitwise reproducible (a resumed job has to rebuild the
+// same batches), so there are no float atomics anywhere: a fixed grid, each
+// block owns a contiguous row slab and writes ONE partial per element to a
+// [blocks, elems] slab, and a second tiny kernel folds the slab in block
+// order. Every reduction (lane tree, wave order, block order) is fixed by
+// the launch shape alone.
+// ---------------------------------------------------------------------------
+
+#define RSDL_STATS_THREADS 256
+#define RSDL_STATS_WAVES (RSDL_STATS_THREADS / 64)
+// Columns at least this wide put lanes across the elements of a row
+// (coalesced along the row, no cross-lane reduction); narrower ones put
+// lanes across rows.
+#define RSDL_STATS_WIDE 64
+
+struct StatsCol {
+  int32_t packed_off;  // byte offset of the column inside a packed row
+  int32_t src_dtype;   // dtype inside the packed row
+  int32_t numel;       // elements per row
+  int32_t elem_base;   // index of element 0 in the flat [elems] outputs
+};
+
+struct StatsTable {
+  StatsCol cols[RSDL_MAX_COLS];
+};
+
+__device__ __forceinline__ bool finite_f64(double v) {
+  // Bit test: independent of any fast-math treatment of isfinite().
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return (b & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+__device__ __forceinline__ bool isnan_f64(double v) {
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
+// Element e of a column in source row `row`, widened to double.
+__device__ __forceinline__ double load_as_f64(
+    const uint8_t* __restrict__ packed, int64_t row_stride, int64_t row,
+    int32_t packed_off, int32_t src_dtype, int32_t e) {
+  const uint8_t* p = packed + row * row_stride + packed_off;
+  switch (src_dtype) {
+    case DT_F64: return reinterpret_cast<const double*>(p)[e];
+    case DT_F32: return (double)reinterpret_cast<const float*>(p)[e];
+    case DT_I64: return (double)reinterpret_cast<const int64_t*>(p)[e];
+    default: return (double)reinterpret_cast<const int32_t*>(p)[e];
+  }
+}
+
+// Pivot of one element: its first finite value among the leading
+// RSDL_STATS_PIVOT_ROWS rows (row 0 whenever that is finite), else 0.0. A
+// pivot near the data keeps Σ(x-p)² - (Σ(x-p))²/n from cancelling; falling
+// straight back to 0.0 on a NaN in row 0 would give that up for a
+// `1e9 + noise` column. Every block derives the same pivot (cached reads).
+#define RSDL_STATS_PIVOT_ROWS 64
+
+__device__ __forceinline__ double stats_pivot(
+    const uint8_t* __restrict__ packed, int64_t row_stride, int64_t n_rows,
+    int32_t packed_off, int32_t src_dtype, int32_t e) {
+  const int64_t lim = min(n_rows, (int64_t)RSDL_STATS_PIVOT_ROWS);
+  for (int64_t r = 0; r < lim; ++r) {
+    const double v =
+        load_as_f64(packed, row_stride, r, packed_off, src_dtype, e);
+    if (finite_f64(v)) return v;
+  }
+  return 0.0;
+}
+
+struct StatsAcc {
+  double s;
+  double ss;
+  int32_t n;  // a block's slab is far below 2^31 rows
+};
+
+__device__ __forceinline__ void stats_add(StatsAcc& a, double x, double p) {
+  if (finite_f64(x)) {
+    const double d = x - p;
+    a.s += d;
+    a.ss += d * d;
+    a.n += 1;
+  }
+}
+
+__global__ __launch_bounds__(RSDL_STATS_THREADS) void column_stats_kernel(
+    const uint8_t* __restrict__ packed,
+    int64_t row_stride,
+    int64_t n_rows,
+    StatsTable table,
+    int32_t num_cols,
+    int32_t total_elems,
+    int64_t* __restrict__ part_n,    // [gridDim.x][total_elems]
+    double* __restrict__ part_s,     // [gridDim.x][total_elems]
+    double* __restrict__ part_ss,    // [gridDim.x][total_elems]
+    double* __restrict__ pivot_out)  // [total_elems]
+{
+  __shared__ double lds_s[RSDL_STATS_WAVES][64];
+  __shared__ double lds_ss[RSDL_STATS_WAVES][64];
+  __shared__ int32_t lds_n[RSDL_STATS_WAVES][64];
+
+  const int32_t lane = threadIdx.x & 63;
+  const int32_t wave = threadIdx.x >> 6;
+  // Contiguous row slab of this block (may be empty for trailing blocks).
+  const int64_t chunk = (n_rows + gridDim.x - 1) / gridDim.x;
+  const int64_t lo = min((int64_t)blockIdx.x * chunk, n_rows);
+  const int64_t hi = min(lo + chunk, n_rows);
+  const int64_t out_base = (int64_t)blockIdx.x * total_elems;
+
+  for (int32_t c = 0; c < num_cols; ++c) {
+    const StatsCol d = table.cols[c];
+    if (d.numel >= RSDL_STATS_WIDE) {
+      // Lanes across the elements of a row, one wave per row; 64-element
+      // chunks of the row are taken in turn so the accumulators stay in
+      // registers whatever the column width.
+      for (int32_t e0 = 0; e0 < d.numel; e0 += 64) {
+        const int32_t e = e0 + lane;
+        const bool live = e < d.numel;
+        double p = 0.0;
+        if (live) {
+          p = stats_pivot(packed, row_stride, n_rows, d.packed_off,
+                          d.src_dtype, e);
+        }
+        StatsAcc a{0.0, 0.0, 0};
+        if (live) {
+          int64_t r = lo + wave;
+          // 4 independent row loads in flight per wave.
+          for (; r + 3 * RSDL_STATS_WAVES < hi; r += 4 * RSDL_STATS_WAVES) {
+            const double x0 = load_as_f64(packed, row_stride, r,
+                                          d.packed_off, d.src_dtype, e);
+            const double x1 = load_as_f64(
+                packed, row_stride, r + RSDL_STATS_WAVES, d.packed_off,
+                d.src_dtype, e);
+            const double x2 = load_as_f64(
+                packed, row_stride, r + 2 * RSDL_STATS_WAVES, d.packed_off,
+                d.src_dtype, e);
+            const double x3 = load_as_f64(
+                packed, row_stride, r + 3 * RSDL_STATS_WAVES, d.packed_off,
+                d.src_dtype, e);
+            stats_add(a, x0, p);
+            stats_add(a, x1, p);
+            stats_add(a, x2, p);
+            stats_add(a, x3, p);
+          }
+          for (; r < hi; r += RSDL_STATS_WAVES) {
+            stats_add(a, load_as_f64(packed, row_stride, r, d.packed_off,
+                                     d.src_dtype, e), p);
+          }
+        }
+        lds_s[wave][lane] = a.s;
+        lds_ss[wave][lane] = a.ss;
+        lds_n[wave][lane] = a.n;
+        __syncthreads();
+        if (wave == 0 && live) {
+          double s = lds_s[0][lane], ss = lds_ss[0][lane];
+          int64_t n = lds_n[0][lane];
+          for (int32_t w = 1; w < RSDL_STATS_WAVES; ++w) {  // fixed order
+            s += lds_s[w][lane];
+            ss += lds_ss[w][lane];
+            n += lds_n[w][lane];
+          }
+          const int64_t o = out_base + d.elem_base + e;
+          part_n[o] = n;
+          part_s[o] = s;
+          part_ss[o] = ss;
+          if (blockIdx.x == 0) pivot_out[d.elem_base + e] = p;
+        }
+        __syncthreads();
+      }
+    } else {
+      // Lanes across rows; fixed shuffle tree inside the wave, then the
+      // waves in order through LDS.
+      for (int32_t e = 0; e < d.numel; ++e) {
+        const double p = stats_pivot(packed, row_stride, n_rows,
+                                     d.packed_off, d.src_dtype, e);
+        StatsAcc a{0.0, 0.0, 0};
+        for (int64_t r = lo + threadIdx.x; r < hi; r += RSDL_STATS_THREADS) {
+          stats_add(a, load_as_f64(packed, row_stride, r, d.packed_off,
+                                   d.src_dtype, e), p);
+        }
+        for (int32_t off = 32; off > 0; off >>= 1) {
+          a.s += __shfl_down(a.s, off, 64);
+          a.ss += __shfl_down(a.ss, off, 64);
+          a.n += __shfl_down(a.n, off, 64);
+        }
+        if (lane == 0) {
+          lds_s[wave][0] = a.s;
+          lds_ss[wave][0] = a.ss;
+          lds_n[wave][0] = a.n;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          double s = lds_s[0][0], ss = lds_ss[0][0];
+          int64_t n = lds_n[0][0];
+          for (int32_t w = 1; w < RSDL_STATS_WAVES; ++w) {  // fixed order
+            s += lds_s[w][0];
+            ss += lds_ss[w][0];
+            n += lds_n[w][0];
+          }
+          const int64_t o = out_base + d.elem_base + e;
+          part_n[o] = n;
+          part_s[o] = s;
+          part_ss[o] = ss;
+          if (blockIdx.x == 0) pivot_out[d.elem_base + e] = p;
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// Fold the [blocks, elems] partial slab in block order: one thread per
+// element, a serial fp64 sum (the slab is a few MB at most).
+__global__ void column_stats_combine_kernel(
+    const int64_t* __restrict__ part_n,
+    const double* __restrict__ part_s,
+    const double* __restrict__ part_ss,
+    int32_t num_blocks,
+    int32_t total_elems,
+    int64_t* __restrict__ out_n,
+    double* __restrict__ out_s,
+    double* __restrict__ out_ss) {
+  const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total_elems) return;
+  int64_t n = 0;
+  double s = 0.0, ss = 0.0;
+  for (int32_t b = 0; b < num_blocks; ++b) {
+    const int64_t o = (int64_t)b * total_elems + e;
+    n += part_n[o];
+    s += part_s[o];
+    ss += part_ss[o];
+  }
+  out_n[e] = n;
+  out_s[e] = s;
+  out_ss[e] = ss;
+}
+
+// ----- apply ---------------------------------------------------------------
+
+// Per-column index of element 0 in the interleaved (shift, scale) table, or
+// -1 for a column that is not standardized (it takes the plain paths).
+struct AffineBase {
+  int32_t base[RSDL_MAX_COLS];
+};
+
+// The one place the affine arithmetic lives. Pinned fp64 subtract and
+// multiply (no contraction, no reassociation), round-to-nearest to fp32;
+// the caller applies the project's fp32 -> dst conversion.
+__device__ __forceinline__ float affine_f32(double x, double2 a, bool fill,
+                                            float fill_f) {
+  if (fill && isnan_f64(x)) return fill_f;
+  return (float)__dmul_rn(__dsub_rn(x, a.x), a.y);
+}
+
+template <typename D>
+__device__ __forceinline__ void store4(D* dst, float y0, float y1, float y2,
+                                       float y3);
+template <>
+__device__ __forceinline__ void store4<float>(float* dst, float y0, float y1,
+                                              float y2, float y3) {
+  *reinterpret_cast<float4*>(dst) = make_float4(y0, y1, y2, y3);
+}
+template <>
+__device__ __forceinline__ void store4<__hip_bfloat16>(
+    __hip_bfloat16* dst, float y0, float y1, float y2, float y3) {
+  union {
+    __hip_bfloat16 h[4];
+    uint2 u;
+  } o;
+  o.h[0] = __float2bfloat16(y0);
+  o.h[1] = __float2bfloat16(y1);
+  o.h[2] = __float2bfloat16(y2);
+  o.h[3] = __float2bfloat16(y3);
+  *reinterpret_cast<uint2*>(dst) = o.u;
+}
+
+// f64 source, numel % 4 == 0: four elements per lane, packed 8-B (bf16) or
+// 16-B (f32) stores. ALIGNED16: the element address is 16-B aligned, so the
+// four doubles arrive as two 16-B loads; otherwise (e.g. the feature matrix
+// behind an int64 key, offset 8) as four 8-B loads.
+template <typename D, bool ALIGNED16>
+__device__ __forceinline__ void unpack_affine_vec4_f64(
+    const uint8_t* __restrict__ packed, int64_t row_stride,
+    const int64_t* __restrict__ perm, D* __restrict__ dst,
+    const double2* __restrict__ aff, int32_t packed_off, int32_t numel,
+    int64_t n_rows, int64_t tid, int64_t nthreads, bool fill, float fill_f) {
+  const int32_t groups = numel >> 2;
+  const int64_t total = n_rows * groups;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / groups;
+    const int64_t g = i - row * groups;
+    const int64_t srow = perm ? perm[row] : row;
+    const uint8_t* sp = packed + srow * row_stride + packed_off + (g << 5);
+    double x0, x1, x2, x3;
+    if (ALIGNED16) {
+      const double2 v0 = reinterpret_cast<const double2*>(sp)[0];
+      const double2 v1 = reinterpret_cast<const double2*>(sp)[1];
+      x0 = v0.x; x1 = v0.y; x2 = v1.x; x3 = v1.y;
+    } else {
+      const double* dp = reinterpret_cast<const double*>(sp);
+      x0 = dp[0]; x1 = dp[1]; x2 = dp[2]; x3 = dp[3];
+    }
+    const double2* ap = aff + (g << 2);
+    store4<D>(dst + row * numel + (g << 2),
+              affine_f32(x0, ap[0], fill, fill_f),
+              affine_f32(x1, ap[1], fill, fill_f),
+              affine_f32(x2, ap[2], fill, fill_f),
+              affine_f32(x3, ap[3], fill, fill_f));
+  }
+}
+
+// f32 source, numel % 4 == 0, 16-B-aligned element address: the float4
+// pattern of the plain kernel.
+template <typename D>
+__device__ __forceinline__ void unpack_affine_vec4_f32(
+    const uint8_t* __restrict__ packed, int64_t row_stride,
+    const int64_t* __restrict__ perm, D* __restrict__ dst,
+    const double2* __restrict__ aff, int32_t packed_off, int32_t numel,
+    int64_t n_rows, int64_t tid, int64_t nthreads, bool fill, float fill_f) {
+  const int32_t groups = numel >> 2;
+  const int64_t total = n_rows * groups;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / groups;
+    const int64_t g = i - row * groups;
+    const int64_t srow = perm ? perm[row] : row;
+    const float4 v = *reinterpret_cast<const float4*>(
+        packed + srow * row_stride + packed_off + (g << 4));
+    const double2* ap = aff + (g << 2);
+    store4<D>(dst + row * numel + (g << 2),
+              affine_f32((double)v.x, ap[0], fill, fill_f),
+              affine_f32((double)v.y, ap[1], fill, fill_f),
+              affine_f32((double)v.z, ap[2], fill, fill_f),
+              affine_f32((double)v.w, ap[3], fill, fill_f));
+  }
+}
+
+// Scalar generic path: any source dtype, any numel, any alignment.
+template <typename S, typename D>
+__device__ void unpack_affine_col_loop(
+    const uint8_t* __restrict__ packed, int64_t row_stride,
+    const int64_t* __restrict__ perm, D* __restrict__ dst,
+    const double2* __restrict__ aff, int32_t packed_off, int32_t numel,
+    int64_t n_rows, int64_t tid, int64_t nthreads, bool fill, float fill_f) {
+  const int64_t total = n_rows * numel;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / numel;
+    const int64_t e = i - row * numel;
+    const int64_t srow = perm ? perm[row] : row;
+    const S* sp = reinterpret_cast<const S*>(
+        packed + srow * row_stride + packed_off);
+    dst[i] = cast_elem<float, D>(
+        affine_f32((double)sp[e], aff[e], fill, fill_f));
+  }
+}
+
+// Same grid shape and column partitioning as unpack_permute_kernel; a
+// column without a table entry runs exactly the plain code.
+__global__ void unpack_permute_affine_kernel(
+    const uint8_t* __restrict__ packed,
+    int64_t row_stride,
+    const int64_t* __restrict__ perm,
+    ColTable table,
+    AffineBase abase,
+    const double2* __restrict__ aff_table,
+    int32_t num_cols,
+    int64_t n_rows,
+    int32_t has_fill,
+    float fill_f) {
+  const int32_t c = blockIdx.y;
+  if (c >= num_cols) return;
+  const ColDesc d = table.cols[c];
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  // Alignment of element 0 of this column in row 0; row_stride is a
+  // multiple of 16, so it holds for every row.
+  const bool al16 =
+      ((reinterpret_cast<uintptr_t>(packed) + (uintptr_t)d.packed_off) &
+       15) == 0;
+  const int32_t ab = abase.base[c];
+  if (ab < 0) {
+    // Not standardized: the plain kernel's paths, unchanged.
+    if (d.src_dtype == DT_F32 && (d.numel & 3) == 0 &&
+        (d.packed_off & 15) == 0) {
+      if (d.dst_dtype == DT_F32) {
+        unpack_vec4_f32_f32(packed, row_stride, perm,
+                            reinterpret_cast<float*>(d.col_ptr),
+                            d.packed_off, d.numel, n_rows, tid, nthreads);
+        return;
+      }
+      if (d.dst_dtype == DT_BF16) {
+        unpack_vec4_f32_bf16(packed, row_stride, perm,
+                             reinterpret_cast<__hip_bfloat16*>(d.col_ptr),
+                             d.packed_off, d.numel, n_rows, tid, nthreads);
+        return;
+      }
+    }
+    RSDL_DISPATCH_PAIR(
+        d.src_dtype, d.dst_dtype,
+        (unpack_col_loop<S, D>(packed, row_stride, perm,
+                               reinterpret_cast<D*>(d.col_ptr),
+                               d.packed_off, d.numel, n_rows, tid,
+                               nthreads)));
+    return;
+  }
+  const double2* aff = aff_table + ab;
+  const bool fill = has_fill != 0;
+  const bool vec_dst = d.dst_dtype == DT_F32 || d.dst_dtype == DT_BF16;
+  if (vec_dst && (d.numel & 3) == 0 && d.src_dtype == DT_F64) {
+    if (d.dst_dtype == DT_BF16) {
+      __hip_bfloat16* o = reinterpret_cast<__hip_bfloat16*>(d.col_ptr);
+      if (al16)
+        unpack_affine_vec4_f64<__hip_bfloat16, true>(
+            packed, row_stride, perm, o, aff, d.packed_off, d.numel, n_rows,
+            tid, nthreads, fill, fill_f);
+      else
+        unpack_affine_vec4_f64<__hip_bfloat16, false>(
+            packed, row_stride, perm, o, aff, d.packed_off, d.numel, n_rows,
+            tid, nthreads, fill, fill_f);
+    } else {
+      float* o = reinterpret_cast<float*>(d.col_ptr);
+      if (al16)
+        unpack_affine_vec4_f64<float, true>(
+            packed, row_stride, perm, o, aff, d.packed_off, d.numel, n_rows,
+            tid, nthreads, fill, fill_f);
+      else
+        unpack_affine_vec4_f64<float, false>(
+            packed, row_stride, perm, o, aff, d.packed_off, d.numel, n_rows,
+            tid, nthreads, fill, fill_f);
+    }
+    return;
+  }
+  if (vec_dst && (d.numel & 3) == 0 && d.src_dtype == DT_F32 && al16) {
+    if (d.dst_dtype == DT_BF16)
+      unpack_affine_vec4_f32<__hip_bfloat16>(
+          packed, row_stride, perm,
+          reinterpret_cast<__hip_bfloat16*>(d.col_ptr), aff, d.packed_off,
+          d.numel, n_rows, tid, nthreads, fill, fill_f);
+    else
+      unpack_affine_vec4_f32<float>(
+          packed, row_stride, perm, reinterpret_cast<float*>(d.col_ptr),
+          aff, d.packed_off, d.numel, n_rows, tid, nthreads, fill, fill_f);
+    return;
+  }
+  RSDL_DISPATCH_PAIR(
+      d.src_dtype, d.dst_dtype,
+      (unpack_affine_col_loop<S, D>(packed, row_stride, perm,
+                                    reinterpret_cast<D*>(d.col_ptr), aff,
+                                    d.packed_off, d.numel, n_rows, tid,
+                                    nthreads, fill, fill_f)));
+}
+
+void launch_column_stats(
+    const void* packed, int64_t row_stride, int64_t n_rows,
+    const StatsTable& table, int32_t num_cols, int32_t total_elems,
+    int32_t num_blocks, int64_t* part_n, double* part_s, double* part_ss,
+    double* pivot, int64_t* out_n, double* out_s, double* out_ss,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(column_stats_kernel, dim3(num_blocks),
+                     dim3(RSDL_STATS_THREADS), 0, stream,
+                     reinterpret_cast<const uint8_t*>(packed), row_stride,
+                     n_rows, table, num_cols, total_elems, part_n, part_s,
+                     part_ss, pivot);
+  const int threads = 64;
+  hipLaunchKernelGGL(column_stats_combine_kernel,
+                     dim3((total_elems + threads - 1) / threads),
+                     dim3(threads), 0, stream, part_n, part_s, part_ss,
+                     num_blocks, total_elems, out_n, out_s, out_ss);
+}
+
+void launch_unpack_permute_affine(
+    const void* packed, int64_t row_stride, const int64_t* perm,
+    const ColTable& table, const AffineBase& abase, const void* aff_table,
+    int32_t num_cols, int64_t n_rows, int32_t has_fill, float fill_f,
+    hipStream_t stream) {
+  const int threads = 256;
+  int64_t bx = (n_rows + threads - 1) / threads;
+  if (bx > 4096) bx = 4096;
+  if (bx < 1) bx = 1;
+  dim3 grid((uint32_t)bx, (uint32_t)num_cols);
+  hipLaunchKernelGGL(unpack_permute_affine_kernel, grid, dim3(threads), 0,
+                     stream, reinterpret_cast<const uint8_t*>(packed),
+                     row_stride, perm, table, abase,
+                     reinterpret_cast<const double2*>(aff_table), num_cols,
+                     n_rows, has_fill, fill_f);
+}
+
 }  // namespace rsdl

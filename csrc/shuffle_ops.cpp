@@ -50,6 +50,33 @@ void launch_unpack_permute(const void* packed, int64_t row_stride,
 void launch_pack_columns(void* packed, int64_t row_stride, const int64_t* perm,
                          const ColTable& table, int32_t num_cols,
                          int64_t n_rows, hipStream_t stream);
+struct StatsCol {
+  int32_t packed_off;
+  int32_t src_dtype;
+  int32_t numel;
+  int32_t elem_base;
+};
+
+struct StatsTable {
+  StatsCol cols[128];
+};
+
+struct AffineBase {
+  int32_t base[128];
+};
+
+void launch_column_stats(const void* packed, int64_t row_stride,
+                         int64_t n_rows, const StatsTable& table,
+                         int32_t num_cols, int32_t total_elems,
+                         int32_t num_blocks, int64_t* part_n, double* part_s,
+                         double* part_ss, double* pivot, int64_t* out_n,
+                         double* out_s, double* out_ss, hipStream_t stream);
+void launch_unpack_permute_affine(const void* packed, int64_t row_stride,
+                                  const int64_t* perm, const ColTable& table,
+                                  const AffineBase& abase,
+                                  const void* aff_table, int32_t num_cols,
+                                  int64_t n_rows, int32_t has_fill,
+                                  float fill_f, hipStream_t stream);
 void launch_partition_hist(const int32_t* dest, int32_t* block_counts,
                            int64_t n, int32_t num_dests, int32_t num_blocks,
                            hipStream_t stream);
@@ -209,6 +236,145 @@ void unpack_permute(const at::Tensor& packed,
   }
   launch_unpack_permute(packed.data_ptr(), stride, perm_ptr, table,
                         (int32_t)outs.size(), n_rows, current_stream());
+}
+
+int64_t src_elem_bytes(int64_t code) {
+  switch (code) {
+    case DT_F64: case DT_I64: return 8;
+    case DT_F32: case DT_I32: return 4;
+    default:
+      TORCH_CHECK(false, "unsupported packed source dtype code ", code);
+  }
+}
+
+// Affine variant of unpack_permute: a column c with aff_base[c] >= 0 comes
+// out as cast((float)((double(x) - shift[e]) * scale[e])), (shift, scale)
+// interleaved per element in aff_table[aff_base[c] + e]; the others exactly
+// as unpack_permute gives them. With nan_fill, a NaN source element of a
+// standardized column becomes cast((float)nan_fill).
+void unpack_permute_affine(const at::Tensor& packed,
+                           const c10::optional<at::Tensor>& perm,
+                           const std::vector<at::Tensor>& outs,
+                           const std::vector<int64_t>& packed_offsets,
+                           const std::vector<int64_t>& src_dtype_codes,
+                           const at::Tensor& aff_table,
+                           const std::vector<int64_t>& aff_base,
+                           const c10::optional<double>& nan_fill) {
+  TORCH_CHECK(packed.is_cuda(), "packed must be on GPU");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.is_contiguous(),
+              "packed must be contiguous uint8 [rows, row_stride]");
+  TORCH_CHECK(outs.size() == packed_offsets.size() &&
+                  outs.size() == src_dtype_codes.size() &&
+                  outs.size() == aff_base.size(),
+              "descriptor length mismatch");
+  TORCH_CHECK(outs.size() <= 128, "at most 128 columns per launch");
+  TORCH_CHECK(aff_table.is_cuda() && aff_table.scalar_type() == at::kDouble &&
+                  aff_table.is_contiguous() && aff_table.dim() == 2 &&
+                  aff_table.size(1) == 2,
+              "aff_table must be contiguous float64 [elems, 2] on GPU");
+  int64_t stride = packed.size(1);
+  TORCH_CHECK(stride % 16 == 0, "row stride must be a multiple of 16");
+  int64_t n_rows;
+  const int64_t* perm_ptr = nullptr;
+  if (perm.has_value()) {
+    TORCH_CHECK(perm->is_cuda() && perm->scalar_type() == at::kLong &&
+                    perm->is_contiguous(),
+                "perm must be contiguous int64 on GPU");
+    n_rows = perm->numel();
+    perm_ptr = perm->data_ptr<int64_t>();
+  } else {
+    n_rows = packed.size(0);
+  }
+  if (n_rows == 0 || outs.empty()) return;
+  ColTable table{};
+  AffineBase abase{};
+  for (size_t c = 0; c < outs.size(); ++c) {
+    const auto& o = outs[c];
+    TORCH_CHECK(o.is_cuda() && o.is_contiguous(),
+                "output column must be contiguous GPU tensor");
+    TORCH_CHECK(o.size(0) == n_rows, "output rows mismatch");
+    const int64_t numel = o.numel() / n_rows;
+    const int64_t esz = src_elem_bytes(src_dtype_codes[c]);
+    TORCH_CHECK(packed_offsets[c] >= 0 && packed_offsets[c] % esz == 0 &&
+                    packed_offsets[c] + numel * esz <= stride,
+                "column ", c, " does not fit the packed row");
+    TORCH_CHECK(aff_base[c] < 0 ||
+                    aff_base[c] + numel <= aff_table.size(0),
+                "affine table too short for column ", c);
+    table.cols[c] = ColDesc{
+        reinterpret_cast<int64_t>(o.data_ptr()),
+        (int32_t)packed_offsets[c],
+        (int32_t)src_dtype_codes[c],
+        dtype_code(o.scalar_type()),
+        (int32_t)numel,
+    };
+    abase.base[c] = aff_base[c] < 0 ? -1 : (int32_t)aff_base[c];
+  }
+  launch_unpack_permute_affine(
+      packed.data_ptr(), stride, perm_ptr, table, abase,
+      aff_table.data_ptr(), (int32_t)outs.size(), n_rows,
+      nan_fill.has_value() ? 1 : 0,
+      nan_fill.has_value() ? (float)*nan_fill : 0.0f, current_stream());
+}
+
+// One read-only pass over a packed block: per element of the listed columns
+// (count of finite values, sum(x - p), sum((x - p)^2), p) in fp64 about the
+// pivot p = the element's first finite value among the leading 64 rows
+// (row 0 as a rule; 0 if there is none). Fixed grid sized
+// from the CU count, per-block partial slab folded in block order: the same
+// input gives the same bits on every call. Returns (count int64 [E],
+// sum [E], sumsq [E], pivot [E]) on the device.
+std::vector<at::Tensor> column_stats(
+    const at::Tensor& packed, const std::vector<int64_t>& packed_offsets,
+    const std::vector<int64_t>& src_dtype_codes,
+    const std::vector<int64_t>& numels) {
+  TORCH_CHECK(packed.is_cuda(), "packed must be on GPU");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.is_contiguous(),
+              "packed must be contiguous uint8 [rows, row_stride]");
+  TORCH_CHECK(packed_offsets.size() == src_dtype_codes.size() &&
+                  packed_offsets.size() == numels.size(),
+              "descriptor length mismatch");
+  TORCH_CHECK(!numels.empty() && numels.size() <= 128,
+              "1..128 columns per launch");
+  const int64_t n_rows = packed.size(0);
+  const int64_t stride = packed.size(1);
+  TORCH_CHECK(n_rows > 0, "column_stats needs at least one row");
+  StatsTable table{};
+  int64_t total = 0;
+  for (size_t c = 0; c < numels.size(); ++c) {
+    const int64_t esz = src_elem_bytes(src_dtype_codes[c]);
+    TORCH_CHECK(numels[c] >= 1 && packed_offsets[c] >= 0 &&
+                    packed_offsets[c] % esz == 0 &&
+                    packed_offsets[c] + numels[c] * esz <= stride,
+                "column ", c, " does not fit the packed row");
+    table.cols[c] = StatsCol{(int32_t)packed_offsets[c],
+                             (int32_t)src_dtype_codes[c],
+                             (int32_t)numels[c], (int32_t)total};
+    total += numels[c];
+  }
+  TORCH_CHECK(total < (1 << 24), "too many elements");
+  int cus = 0;
+  C10_HIP_CHECK(hipDeviceGetAttribute(
+      &cus, hipDeviceAttributeMultiprocessorCount, packed.get_device()));
+  const int32_t num_blocks = std::max(1, cus) * 8;
+  auto opt_d = packed.options().dtype(at::kDouble);
+  auto opt_l = packed.options().dtype(at::kLong);
+  auto part_n = at::empty({num_blocks, total}, opt_l);
+  auto part_s = at::empty({num_blocks, total}, opt_d);
+  auto part_ss = at::empty({num_blocks, total}, opt_d);
+  auto pivot = at::empty({total}, opt_d);
+  auto out_n = at::empty({total}, opt_l);
+  auto out_s = at::empty({total}, opt_d);
+  auto out_ss = at::empty({total}, opt_d);
+  launch_column_stats(packed.data_ptr(), stride, n_rows, table,
+                      (int32_t)numels.size(), (int32_t)total, num_blocks,
+                      part_n.data_ptr<int64_t>(), part_s.data_ptr<double>(),
+                      part_ss.data_ptr<double>(), pivot.data_ptr<double>(),
+                      out_n.data_ptr<int64_t>(), out_s.data_ptr<double>(),
+                      out_ss.data_ptr<double>(), current_stream());
+  return {out_n, out_s, out_ss, pivot};
 }
 
 // packed[perm[i]*stride + off_c + e*esz] = cast(cols[c][i*numel+e])
@@ -742,6 +908,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("unpack_permute", &rsdl::unpack_permute, py::arg("packed"),
         py::arg("perm"), py::arg("outs"), py::arg("packed_offsets"),
         py::arg("src_dtype_codes"));
+  m.def("unpack_permute_affine", &rsdl::unpack_permute_affine,
+        py::arg("packed"), py::arg("perm"), py::arg("outs"),
+        py::arg("packed_offsets"), py::arg("src_dtype_codes"),
+        py::arg("aff_table"), py::arg("aff_base"),
+        py::arg("nan_fill") = c10::nullopt);
+  m.def("column_stats", &rsdl::column_stats, py::arg("packed"),
+        py::arg("packed_offsets"), py::arg("src_dtype_codes"),
+        py::arg("numels"));
   m.def("pack_columns", &rsdl::pack_columns, py::arg("cols"),
         py::arg("packed_offsets"), py::arg("packed_dtype_codes"),
         py::arg("row_stride"), py::arg("perm") = c10::nullopt);

@@ -186,6 +186,19 @@ class ShufflingDataset:
         iterator each epoch (reference dataset.py:96-106)."""
         self._epoch = epoch
 
+    def column_stats(self, timeout: Optional[float] = None):
+        """Statistics the engine standardizes with (``normalize=...``):
+        ``{name: ColumnStats(count, mean, std)}``. Blocks until the fit is
+        done. Only the process that runs the engine has them."""
+        if self._engine is None:
+            raise RuntimeError(
+                "column_stats() is only available in the process that runs "
+                "the shuffle engine (rank 0 in local mode, every rank in "
+                "distributed mode); this trainer only connects to rank 0's "
+                "queue"
+            )
+        return self._engine.column_stats(timeout)
+
     def __iter__(self):
         """Yields RowBlock batches of ``batch_size`` rows from the shuffle
         queue (reference dataset.py:108-188)."""

@@ -36,7 +36,7 @@ import os
 import sys
 import threading
 import time
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 _VERBOSE = os.environ.get("RSDL_VERBOSE") == "1"
 
@@ -54,8 +54,13 @@ from ray_shuffling_data_loader_amd.io import (
     read_files_packed,
 )
 from ray_shuffling_data_loader_amd.ops.shuffle_ops import (
+    ColumnStats,
+    column_stats,
     gather_rows,
+    make_affine_table,
+    merge_column_stats,
     partition_rows,
+    stats_to_affine,
     unpack_permute,
 )
 from ray_shuffling_data_loader_amd.parallel import fabric
@@ -99,6 +104,8 @@ class ShuffleEngine:
         output: str = "auto",  # "auto" | "views" | "columns"
         out_dtypes: Optional[Dict[str, torch.dtype]] = None,
         stats_collector=None,
+        normalize: Union[None, str, Sequence[str], Dict] = None,
+        nan_fill: Optional[float] = None,
     ):
         self.filenames = list(filenames)
         self.consumer = consumer
@@ -197,6 +204,161 @@ class ShuffleEngine:
         self._error: Optional[BaseException] = None
         self.duration: Optional[float] = None
 
+        # Feature standardization (MI355X extension, off by default): the
+        # statistics are fitted once on the first packed source block, or
+        # given, and frozen for the life of the engine.
+        self.normalize = normalize
+        self.nan_fill = nan_fill
+        self._stats_ready = threading.Event()
+        self._col_stats: Optional[Dict[str, ColumnStats]] = None
+        self._affine = None
+        self._norm_names: List[str] = []
+        if normalize is None:
+            if nan_fill is not None:
+                raise ValueError("nan_fill needs normalize")
+        else:
+            self._init_normalize(normalize)
+
+    # ----- standardization ---------------------------------------------------
+
+    _NORM_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+
+    def _init_normalize(self, normalize) -> None:
+        schema = self.out_schema
+        given = None
+        if isinstance(normalize, str):
+            if normalize != "standard":
+                raise ValueError(
+                    f"normalize={normalize!r}: expected 'standard', a list "
+                    "of column names or a {name: (mean, std)} dict"
+                )
+            names = [
+                c.name for c in schema.columns if c.dtype in self._NORM_DTYPES
+            ]
+        elif isinstance(normalize, dict):
+            names = list(normalize)
+            given = normalize
+        else:
+            names = list(normalize)
+        for name in names:
+            if name not in schema.names:
+                raise ValueError(
+                    f"normalize: {name!r} is not a column of the output "
+                    f"schema {schema.names}"
+                )
+            if schema.col(name).dtype not in self._NORM_DTYPES:
+                raise TypeError(
+                    f"normalize: column {name!r} has non-numeric dtype "
+                    f"{schema.col(name).dtype}"
+                )
+            # A standardized integer column leaves the kernel as float32
+            # unless the caller chose a dtype.
+            if (
+                not schema.col(name).dtype.is_floating_point
+                and name not in self.out_dtypes
+            ):
+                self.out_dtypes = dict(self.out_dtypes)
+                self.out_dtypes[name] = torch.float32
+        self._norm_names = names
+        if given is not None:
+            # Precomputed statistics (e.g. a validation set standardized
+            # with the training set's): applied exactly as given, no fit.
+            stats = {}
+            for name in names:
+                mean, std = given[name]
+                numel = schema.col(name).numel
+                mean = torch.as_tensor(mean, dtype=torch.float64).reshape(-1)
+                std = torch.as_tensor(std, dtype=torch.float64).reshape(-1)
+                if mean.numel() == 1 and numel > 1:
+                    mean = mean.expand(numel)
+                if std.numel() == 1 and numel > 1:
+                    std = std.expand(numel)
+                if mean.numel() != numel or std.numel() != numel:
+                    raise ValueError(
+                        f"normalize[{name!r}] needs {numel} elements"
+                    )
+                stats[name] = ColumnStats(
+                    torch.full((numel,), -1, dtype=torch.int64),
+                    mean.clone(),
+                    std.clone(),
+                )
+            self._freeze_stats(stats)
+
+    def _freeze_stats(self, stats: Dict[str, ColumnStats]) -> None:
+        # count -1 marks given statistics: there only std == 0 maps to
+        # scale 1.
+        affine = stats_to_affine(
+            {
+                k: ColumnStats(v.count.abs(), v.mean, v.std)
+                for k, v in stats.items()
+            }
+        )
+        self._affine = make_affine_table(affine, self.out_schema, self.device)
+        self._col_stats = stats
+        self._stats_ready.set()
+
+    def _fit(self, src: torch.Tensor) -> None:
+        """Fit the statistics on this rank's packed source block (one
+        read-only kernel pass) and, in distributed mode, merge every rank's
+        (count, mean, M2) in rank order so all ranks hold the same global
+        statistics. A pure function of the files: independent of seed,
+        epoch and start_epoch."""
+        t0 = time.perf_counter()
+        names = self._norm_names
+        local = column_stats(src, self.out_schema, names)
+        if self.distributed:
+            flat = torch.cat(
+                [
+                    torch.cat(
+                        [
+                            local[nm].count.double(),
+                            local[nm].mean,
+                            local[nm].std ** 2 * local[nm].count.double(),
+                        ]
+                    )
+                    for nm in names
+                ]
+            ) if names else torch.zeros(0, dtype=torch.float64)
+            allr = fabric.all_gather_stats(flat, self.group, self.device)
+            per_rank = []
+            for r in range(allr.shape[0]):
+                st, o = {}, 0
+                for nm in names:
+                    k = self.out_schema.col(nm).numel
+                    cnt = allr[r, o : o + k].round().to(torch.int64)
+                    mean = allr[r, o + k : o + 2 * k]
+                    m2 = allr[r, o + 2 * k : o + 3 * k]
+                    std = (m2 / cnt.clamp(min=1).double()).sqrt()
+                    st[nm] = ColumnStats(cnt, mean, std)
+                    o += 3 * k
+                per_rank.append(st)
+            local = merge_column_stats(per_rank)
+        self._freeze_stats(local)
+        _vlog(
+            f"rank {self.rank}: fitted {len(names)} columns in "
+            f"{time.perf_counter() - t0:.3f}s"
+        )
+
+    def column_stats(
+        self, timeout: Optional[float] = None
+    ) -> Dict[str, ColumnStats]:
+        """The frozen statistics of the standardized columns,
+        ``{name: ColumnStats(count, mean, std)}``; blocks until the fit is
+        done and raises if the engine failed first. ``count`` is -1 for
+        statistics that were given rather than fitted."""
+        if self.normalize is None:
+            raise RuntimeError(
+                "this engine does not normalize (normalize=None)"
+            )
+        if not self._stats_ready.wait(timeout):
+            raise TimeoutError("column statistics are not fitted yet")
+        if self._col_stats is None:
+            raise RuntimeError(
+                "shuffle engine worker failed before the statistics were "
+                "fitted"
+            ) from self._error
+        return dict(self._col_stats)
+
     # ----- source ------------------------------------------------------------
 
     def _get_source(self, epoch: int) -> torch.Tensor:
@@ -218,6 +380,10 @@ class ShuffleEngine:
             per_file = read_dur / max(1, len(self.my_files))
             for _ in self.my_files:
                 self.stats.map_done(epoch, per_file, per_file)
+        if self.normalize is not None and self._affine is None:
+            # First read: fit once, before the first partition is built.
+            # Later re-reads (source_cache="none") keep the frozen fit.
+            self._fit(src)
         if self.source_cache in ("auto", "device"):
             self._cached_source = src
         elif self.source_cache == "host":
@@ -258,9 +424,15 @@ class ShuffleEngine:
         hom = homogeneous_dtype(schema)
         # Output dtype casts (e.g. fp32 -> bf16 features) happen inside the
         # fused unpack kernel, which requires the columns path.
-        use_views = not self.out_dtypes and (
-            self.output == "views"
-            or (self.output == "auto" and hom is not None)
+        # Standardization happens in the same kernel, so it too needs the
+        # columns path.
+        use_views = (
+            not self.out_dtypes
+            and self.normalize is None
+            and (
+                self.output == "views"
+                or (self.output == "auto" and hom is not None)
+            )
         )
         if use_views and hom is not None:
             esz = dtype_bytes(hom)
@@ -273,6 +445,16 @@ class ShuffleEngine:
                     cols[spec.name] = typed[:, o]
                 else:
                     cols[spec.name] = typed[:, o : o + spec.numel]
+            return RowBlock(cols)
+        if self._affine is not None:
+            cols = unpack_permute(
+                rows,
+                schema,
+                perm=idx.to(torch.long),
+                out_dtypes=self.out_dtypes,
+                affine=self._affine,
+                nan_fill=self.nan_fill,
+            )
             return RowBlock(cols)
         cols = unpack_permute(
             rows, schema, perm=idx.to(torch.long), out_dtypes=self.out_dtypes
@@ -412,6 +594,9 @@ class ShuffleEngine:
                 self.run()
             except BaseException as e:  # surfaced via join() AND the queue
                 self._error = e
+                # Wake column_stats() waiters: a failed engine must not
+                # block them forever.
+                self._stats_ready.set()
                 failure = ShuffleEngineFailure(e)
                 # Per-(epoch, trainer) scope: delivering into an epoch that
                 # was already consumed/evicted (or a shut-down queue) may

@@ -14,7 +14,7 @@ Reference ops replaced here: ``pd.concat`` + ``df.sample(frac=1)``
 -> :func:`unpack_permute`.
 """
 
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import os
 
@@ -161,20 +161,80 @@ def pack_columns(
     return packed
 
 
+class AffineTable:
+    """Per-element (shift, scale) of the standardized columns of one schema,
+    validated once and, for a GPU device, uploaded once as the interleaved
+    float64 ``[elems, 2]`` table the affine unpack kernel reads. Build it
+    with :func:`make_affine_table`; :func:`unpack_permute` also accepts the
+    plain ``{name: (shift, scale)}`` dict and builds one per call."""
+
+    def __init__(self, entries, base, table):
+        self.entries = entries  # name -> (shift[numel], scale[numel]) cpu f64
+        self.base = base  # name -> index of element 0 in ``table``
+        self.table = table  # float64 [elems, 2] on the device, or None (CPU)
+
+
+def make_affine_table(
+    affine: Dict[str, Tuple[torch.Tensor, torch.Tensor]],
+    schema: Schema,
+    device=None,
+) -> AffineTable:
+    entries, base, rows = {}, {}, []
+    n_elems = 0
+    for name, (shift, scale) in affine.items():
+        spec = schema.col(name)
+        pair = []
+        for t in (shift, scale):
+            t = torch.as_tensor(t, dtype=torch.float64).detach().cpu()
+            t = t.reshape(-1)
+            if t.numel() == 1 and spec.numel > 1:
+                t = t.expand(spec.numel)
+            if t.numel() != spec.numel:
+                raise ValueError(
+                    f"affine entry for column {name!r} needs {spec.numel} "
+                    f"elements, got {t.numel()}"
+                )
+            pair.append(t.contiguous())
+        entries[name] = (pair[0], pair[1])
+        base[name] = n_elems
+        n_elems += spec.numel
+        rows.append(torch.stack(pair, dim=1))
+    table = None
+    if device is not None and torch.device(device).type == "cuda":
+        table = torch.cat(rows).contiguous().to(device)
+    return AffineTable(entries, base, table)
+
+
 def unpack_permute(
     packed: torch.Tensor,
     schema: Schema,
     perm: Optional[torch.Tensor] = None,
     out_dtypes: Optional[Dict[str, torch.dtype]] = None,
+    affine: Union[
+        None, AffineTable, Dict[str, Tuple[torch.Tensor, torch.Tensor]]
+    ] = None,
+    nan_fill: Optional[float] = None,
 ) -> Dict[str, torch.Tensor]:
     """Fused gather-permute + per-column cast + pack into contiguous torch
     column tensors: out[name][i] = cast(packed[perm[i], off_name]).
 
     This single op replaces the reference's reduce-side
     concat+sample+convert_to_tensor chain (shuffle.py:192-194 +
-    torch_dataset.py:204-236)."""
+    torch_dataset.py:204-236).
+
+    ``affine`` (MI355X extension) maps a column name to float64
+    ``(shift[numel], scale[numel])``; element e of such a column comes out as
+    ``cast((float)((double(x) - shift[e]) * scale[e]))`` — standardized in
+    fp64 BEFORE the narrowing cast, in the same kernel pass. With
+    ``nan_fill``, a NaN source element of such a column becomes
+    ``cast((float)nan_fill)``. Columns not named come out exactly as without
+    the keyword; ``affine=None`` launches the plain kernel."""
     out_dtypes = out_dtypes or {}
     n = perm.numel() if perm is not None else packed.shape[0]
+    if affine is not None and not isinstance(affine, AffineTable):
+        affine = make_affine_table(affine, schema, packed.device)
+    if affine is not None and not affine.entries:
+        affine = None
     if packed.is_cuda:
         hip = _load_hip()
         outs, offs, codes = [], [], []
@@ -187,7 +247,18 @@ def unpack_permute(
             offs.append(schema.offsets[spec.name])
             codes.append(_dtype_code(spec.dtype))
             result[spec.name] = o
-        hip.unpack_permute(packed, perm, outs, offs, codes)
+        if affine is None:
+            hip.unpack_permute(packed, perm, outs, offs, codes)
+            return result
+        table = affine.table
+        if table is None or table.device != packed.device:
+            table = make_affine_table(
+                affine.entries, schema, packed.device
+            ).table
+        bases = [affine.base.get(spec.name, -1) for spec in schema.columns]
+        hip.unpack_permute_affine(
+            packed, perm, outs, offs, codes, table, bases, nan_fill
+        )
         return result
     packed_np = packed.numpy()
     perm_np = perm.cpu().numpy() if perm is not None else None
@@ -200,12 +271,199 @@ def unpack_permute(
         )
         t = torch.from_numpy(arr)
         dst_dt = out_dtypes.get(spec.name, spec.dtype)
-        if dst_dt != spec.dtype:
+        if affine is not None and spec.name in affine.entries:
+            # The bit-exact oracle of the affine kernel: fp64 subtract, fp64
+            # multiply, round to fp32, then the fp32 -> dst conversion.
+            shift, scale = affine.entries[spec.name]
+            x = t.double()
+            y = ((x - shift) * scale).float()
+            if nan_fill is not None:
+                y = torch.where(
+                    torch.isnan(x),
+                    torch.tensor(float(nan_fill), dtype=torch.float64)
+                    .float(),
+                    y,
+                )
+            t = y.to(dst_dt)
+        elif dst_dt != spec.dtype:
             t = t.to(dst_dt)
         if spec.numel == 1:
             t = t.reshape(n)
         result[spec.name] = t
     return result
+
+
+# ---------------------------------------------------------------------------
+# Column statistics: the fit behind ShuffleEngine(normalize=...).
+# ---------------------------------------------------------------------------
+
+
+class ColumnStats(NamedTuple):
+    """Per-element statistics of one column over its finite values:
+    ``count`` int64, ``mean`` and population ``std`` (ddof=0) float64, each
+    of shape ``[numel]`` (host tensors)."""
+
+    count: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+
+
+_STATS_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+_STATS_PIVOT_ROWS = 64  # RSDL_STATS_PIVOT_ROWS in csrc/shuffle_kernels.hip
+
+
+def _finish_stats(count, s, ss, pivot) -> ColumnStats:
+    """(count, sum(x-p), sum((x-p)^2), p) -> ColumnStats, fp64 on the host.
+    Shared by the CPU and GPU paths."""
+    count = count.to(torch.int64)
+    nz = count > 0
+    cnt = count.clamp(min=1).double()
+    dmean = s / cnt
+    var = (ss / cnt - dmean * dmean).clamp_(min=0.0)
+    zero = torch.zeros_like(dmean)
+    mean = torch.where(nz, pivot + dmean, zero)
+    std = torch.where(nz, var.sqrt(), zero)
+    return ColumnStats(count, mean, std)
+
+
+def column_stats(
+    packed: torch.Tensor,
+    schema: Schema,
+    columns: Optional[Sequence[str]] = None,
+) -> Dict[str, ColumnStats]:
+    """Per-element count / mean / population std of packed columns, skipping
+    non-finite values, accumulated in fp64 about a per-element pivot (the
+    first finite value, row 0 as a rule): a constant column has std exactly 0 and a ``1e9 + noise``
+    column does not cancel. Integer columns accumulate as double.
+
+    GPU: one read-only pass of the ``column_stats`` HIP kernel with a fixed
+    grid and a block-ordered partial fold — no float atomics, so the same
+    block gives the same bits on every call. CPU: numpy fp64 over the
+    strided column views (the oracle). Results are host tensors."""
+    names = list(columns) if columns is not None else [
+        c.name for c in schema.columns if c.dtype in _STATS_DTYPES
+    ]
+    specs = [schema.col(nm) for nm in names]
+    for spec in specs:
+        if spec.dtype not in _STATS_DTYPES:
+            raise TypeError(
+                f"column_stats: unsupported dtype {spec.dtype} for column "
+                f"{spec.name!r}"
+            )
+    n = packed.shape[0]
+    if n == 0 or not specs:
+        return {
+            spec.name: ColumnStats(
+                torch.zeros(spec.numel, dtype=torch.int64),
+                torch.zeros(spec.numel, dtype=torch.float64),
+                torch.zeros(spec.numel, dtype=torch.float64),
+            )
+            for spec in specs
+        }
+    if packed.is_cuda:
+        hip = _load_hip()
+        result = {}
+        # RSDL_MAX_COLS columns per launch, as the ColTable ops.
+        for lo in range(0, len(specs), 128):
+            chunk = specs[lo : lo + 128]
+            cnt, s, ss, piv = hip.column_stats(
+                packed,
+                [schema.offsets[c.name] for c in chunk],
+                [_dtype_code(c.dtype) for c in chunk],
+                [c.numel for c in chunk],
+            )
+            cnt, s, ss, piv = cnt.cpu(), s.cpu(), ss.cpu(), piv.cpu()
+            e0 = 0
+            for c in chunk:
+                sl = slice(e0, e0 + c.numel)
+                result[c.name] = _finish_stats(
+                    cnt[sl], s[sl], ss[sl], piv[sl]
+                )
+                e0 += c.numel
+        return result
+    packed_np = packed.numpy()
+    result = {}
+    for spec in specs:
+        np_dt = TORCH_TO_NUMPY_DTYPE[spec.dtype]
+        x = _np_strided_view(
+            packed_np, schema, spec.name, spec.numel, np_dt
+        ).astype(np.float64)
+        fin = np.isfinite(x)
+        # Pivot: the first finite value among the leading rows (row 0 as a
+        # rule), 0.0 if there is none — the kernel's rule.
+        head = fin[:_STATS_PIVOT_ROWS]
+        first = head.argmax(0)
+        piv = np.where(
+            head.any(0), x[first, np.arange(x.shape[1])], 0.0
+        )
+        d = np.where(fin, x - piv, 0.0)
+        result[spec.name] = _finish_stats(
+            torch.from_numpy(fin.sum(0)),
+            torch.from_numpy(d.sum(0)),
+            torch.from_numpy((d * d).sum(0)),
+            torch.from_numpy(piv),
+        )
+    return result
+
+
+def merge_column_stats(
+    stats_list: Sequence[Dict[str, ColumnStats]],
+) -> Dict[str, ColumnStats]:
+    """Pairwise (Chan) merge of per-shard statistics as (count, mean, M2) in
+    fp64, folded in list order — every caller that merges the same list gets
+    the same bits. Empty shards (count 0) are neutral."""
+    merged: Dict[str, ColumnStats] = {}
+    if not stats_list:
+        return merged
+    for name in stats_list[0]:
+        n_a = m_a = m2_a = None
+        for st in stats_list:
+            c = st[name]
+            n_b = c.count.to(torch.int64)
+            m_b = c.mean.double()
+            m2_b = c.std.double() ** 2 * n_b.double()
+            if n_a is None:
+                n_a, m_a, m2_a = n_b.clone(), m_b.clone(), m2_b.clone()
+                continue
+            n = n_a + n_b
+            nd = n.clamp(min=1).double()
+            delta = m_b - m_a
+            w_b = n_b.double() / nd
+            # An empty side contributes nothing (and must not move the mean
+            # by a rounding of delta * 0).
+            m = torch.where(n_b == 0, m_a, torch.where(
+                n_a == 0, m_b, m_a + delta * w_b))
+            m2 = m2_a + m2_b + delta * delta * (n_a.double() * w_b)
+            m2 = torch.where(n_b == 0, m2_a, torch.where(
+                n_a == 0, m2_b, m2))
+            n_a, m_a, m2_a = n, m, m2
+        nz = n_a > 0
+        nd = n_a.clamp(min=1).double()
+        zero = torch.zeros_like(m_a)
+        merged[name] = ColumnStats(
+            n_a,
+            torch.where(nz, m_a, zero),
+            torch.where(nz, (m2_a / nd).clamp(min=0.0).sqrt(), zero),
+        )
+    return merged
+
+
+def stats_to_affine(
+    stats: Dict[str, ColumnStats],
+) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """ColumnStats -> (shift, scale) with scale = 1/std in fp64 on the host,
+    or 1.0 where std == 0 or count == 0 (the StandardScaler convention: a
+    constant column becomes 0). The kernel never divides."""
+    out = {}
+    for name, st in stats.items():
+        std = st.std.double()
+        ok = (std > 0) & (st.count > 0)
+        scale = torch.where(
+            ok, 1.0 / torch.where(ok, std, torch.ones_like(std)),
+            torch.ones_like(std),
+        )
+        out[name] = (st.mean.double().clone(), scale)
+    return out
 
 
 # ---------------------------------------------------------------------------

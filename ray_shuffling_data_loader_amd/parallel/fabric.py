@@ -98,6 +98,26 @@ def exchange_counts(
     return torch.stack(gathered)[:, rank].cpu().contiguous()
 
 
+def all_gather_stats(
+    local: torch.Tensor, group=None, device=None
+) -> torch.Tensor:
+    """All-gather of one rank's flat float64 statistics vector (the
+    engine's per-element count / mean / M2 for ``normalize``). Returns the
+    ``[world, len]`` stack in RANK order on the host, identical on every
+    rank, so a merge folded in that order gives every rank the same bits.
+    gloo gathers host tensors; RCCL needs device tensors."""
+    world = dist.get_world_size(group)
+    backend = dist.get_backend(group)
+    local = local.to(torch.float64).contiguous()
+    if backend == "nccl":
+        local = local.to(device or "cuda")
+    else:
+        local = local.cpu()
+    gathered = [torch.empty_like(local) for _ in range(world)]
+    dist.all_gather(gathered, local, group=group)
+    return torch.stack(gathered).cpu()
+
+
 def exchange_rows(
     grouped: torch.Tensor,
     send_counts: torch.Tensor,

@@ -48,10 +48,32 @@ class TorchShufflingDataset(IterableDataset):
         label_shape: Optional[int] = None,
         label_type: Optional[torch.dtype] = None,
         feature_matrix: bool = False,
+        normalize_features: bool = False,
         **engine_kwargs,
     ):
         super().__init__()
         self._feature_matrix = feature_matrix
+        if normalize_features and not feature_matrix:
+            names = (
+                list(feature_columns)
+                if isinstance(feature_columns, list)
+                else [feature_columns]
+            )
+            # Standardize the feature columns (never the label) inside the
+            # fused unpack; an explicit normalize= wins.
+            engine_kwargs.setdefault("normalize", names)
+            if engine_kwargs["normalize"] == names:
+                # The requested feature dtypes are produced by the same
+                # kernel pass, after the fp64 standardization.
+                types = feature_types
+                if types and not isinstance(types, list):
+                    types = [types]
+                if not types:
+                    types = [torch.float] * len(names)
+                out_dtypes = dict(engine_kwargs.get("out_dtypes") or {})
+                for name, ft in zip(names, types):
+                    out_dtypes.setdefault(name, ft)
+                engine_kwargs["out_dtypes"] = out_dtypes
         if feature_matrix:
             # Fuse the feature columns into one [N, C] matrix inside the
             # engine's packed layout (io.fuse_schema): zero per-batch conversion.
@@ -66,6 +88,10 @@ class TorchShufflingDataset(IterableDataset):
                     engine_kwargs.setdefault(
                         "out_dtypes", {"__features__": ft}
                     )
+            if normalize_features:
+                engine_kwargs.setdefault(
+                    "normalize", [engine_kwargs["feature_matrix"][0]]
+                )
         self._ds = ShufflingDataset(
             filenames,
             num_epochs,
@@ -91,6 +117,12 @@ class TorchShufflingDataset(IterableDataset):
         """Set the current training epoch; call before constructing the
         iterator each epoch (reference torch_dataset.py:78-88)."""
         self._ds.set_epoch(epoch)
+
+    def feature_stats(self, timeout: Optional[float] = None):
+        """Statistics the features were standardized with
+        (``normalize_features=True`` or an explicit ``normalize=``); see
+        :meth:`ShufflingDataset.column_stats`."""
+        return self._ds.column_stats(timeout)
 
     def __iter__(self):
         for block in iter(self._ds):

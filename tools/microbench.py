@@ -34,10 +34,101 @@ def timeit_gpu(fn, iters=20, warmup=3):
     return t0.elapsed_time(t1) / iters  # ms
 
 
+def median_ms(fn, iters=7, warmup=2):
+    """Median of per-call event timings (ms), and the min..max spread."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        torch.cuda.synchronize()
+        times.append(t0.elapsed_time(t1))
+    times.sort()
+    return times[len(times) // 2], times[0], times[-1]
+
+
+def normalize_bench(dev):
+    """column_stats (the fit) and the affine unpack next to the plain unpack
+    at one shape: RSDL_MB_ROWS rows (default the flagship shard, 12.5e6) of
+    100 f64 features + f64 label, -> bf16 through a random perm."""
+    from ray_shuffling_data_loader_amd.ops import shuffle_ops
+
+    n = int(float(os.environ.get("RSDL_MB_ROWS", "12.5e6")))
+    schema = Schema(
+        [
+            ColumnSpec("features", torch.float64, 100),
+            ColumnSpec("labels", torch.float64, 1),
+        ]
+    )
+    stride = schema.row_stride
+    vals = torch.empty(n, stride // 8, dtype=torch.float64, device=dev)
+    step = 1 << 20
+    for lo in range(0, n, step):  # bounded temporaries
+        vals[lo : lo + step].normal_(mean=1e6, std=3.0)
+    packed = vals.view(torch.uint8)
+    perm = torch.randperm(n, device=dev)
+    src_bytes = n * stride
+    print(f"normalize bench: {n} rows x {stride} B = {src_bytes / 1e9:.2f} GB")
+
+    hip = shuffle_ops._load_hip()
+    offs = [schema.offsets["features"]]
+    codes = [shuffle_ops._dtype_code(torch.float64)]
+    ms, lo_, hi_ = median_ms(
+        lambda: hip.column_stats(packed, offs, codes, [100])
+    )
+    print(
+        f"column_stats f64x100 : {ms:7.3f} ms [{lo_:.3f}..{hi_:.3f}]  "
+        f"{n * 800 / ms / 1e6:7.0f} GB/s of source bytes"
+    )
+    dst = torch.empty_like(packed)
+    ms, lo_, hi_ = median_ms(lambda: dst.copy_(packed))
+    print(
+        f"device copy (same day): {ms:7.3f} ms [{lo_:.3f}..{hi_:.3f}]  "
+        f"{src_bytes / ms / 1e6:7.0f} GB/s read (+ the same written)"
+    )
+    del dst
+
+    stats = shuffle_ops.column_stats(packed, schema, ["features"])
+    affine = shuffle_ops.make_affine_table(
+        shuffle_ops.stats_to_affine(stats), schema, dev
+    )
+    out_dtypes = {"features": torch.bfloat16}
+    moved = n * (800 + 8 + 200 + 8)  # row payload read, columns written
+    for rep in range(3):  # the baseline's own run-to-run spread
+        ms, lo_, hi_ = median_ms(
+            lambda: unpack_permute(
+                packed, schema, perm=perm, out_dtypes=out_dtypes
+            )
+        )
+        print(
+            f"unpack plain  f64->bf16 #{rep}: {ms:7.3f} ms "
+            f"[{lo_:.3f}..{hi_:.3f}]  {moved / ms / 1e6:7.0f} GB/s"
+        )
+    for rep in range(3):
+        ms, lo_, hi_ = median_ms(
+            lambda: unpack_permute(
+                packed, schema, perm=perm, out_dtypes=out_dtypes,
+                affine=affine,
+            )
+        )
+        print(
+            f"unpack affine f64->bf16 #{rep}: {ms:7.3f} ms "
+            f"[{lo_:.3f}..{hi_:.3f}]  {moved / ms / 1e6:7.0f} GB/s"
+        )
+
+
 def main():
     assert torch.cuda.is_available()
     dev = torch.device("cuda", 0)
     print(f"device: {torch.cuda.get_device_name(0)}")
+    if os.environ.get("RSDL_MB_NORMALIZE_ONLY") == "1":
+        normalize_bench(dev)
+        return
 
     n = 2_500_000
     stride = 416  # 100 fp32 features + label + pad
@@ -118,6 +209,8 @@ def main():
         f"pack_columns tiled   : {ms:7.3f} ms  "
         f"{pbytes / ms / 1e6:7.0f} GB/s"
     )
+
+    normalize_bench(dev)
 
     if os.environ.get("RSDL_MB_KERNELS_ONLY") == "1":
         return
