@@ -11,7 +11,11 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+#include <cstring>
 #include <vector>
+
+#include "step_glue.h"
 
 namespace rsdl {
 
@@ -646,6 +650,77 @@ static at::Tensor swizzle_frag(const at::Tensor& W) {
       .view({-1});
 }
 
+// Buffers + launches of the forward chain, shared by fwd_chain_bf16 and
+// fused_step_bf16. Weights arrive fragment-major (W1 with K padded to
+// 112), biases fp32, ``tgt`` fp32 [M] or nullptr. Nothing is launched for
+// M == 0 (the weight tensors may then be undefined).
+struct FwdChainOut {
+  at::Tensor a1t, mask1, a2t, mask2, a3, out, dyb, loss_part;
+};
+
+FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
+                          const at::Tensor& W2s, const at::Tensor& W3s,
+                          const at::Tensor& w4, const at::Tensor& b1f,
+                          const at::Tensor& b2f, const at::Tensor& b3f,
+                          const at::Tensor& b4f, const at::Tensor* tgt,
+                          const c10::optional<at::Tensor>& xt_out,
+                          bool pi16) {
+  FwdChainOut f;
+  const int64_t M = x.size(0);
+  // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
+  // 32-bit relu-mask words per column) — the backward chain consumes
+  // masks, the wgrad kernel consumes the fragments; nothing reads
+  // row-major a1/a2.
+  const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
+  const int64_t mchunks = mtiles * 2;
+  f.a1t = at::empty({16 * mchunks * 512}, x.options());
+  f.a2t = at::empty({8 * mchunks * 512}, x.options());
+  f.mask1 = at::empty({mtiles, 512}, x.options().dtype(at::kInt));
+  f.mask2 = at::empty({mtiles, 256}, x.options().dtype(at::kInt));
+  f.a3 = at::empty({M, 128}, x.options());
+  f.out = at::empty({M, 1}, x.options());
+  const float* tgt_ptr = nullptr;
+  void* dyb_ptr = nullptr;
+  float* lp_ptr = nullptr;
+  if (tgt != nullptr) {
+    f.dyb = at::empty({M, 1}, x.options());
+    f.loss_part = at::empty({std::max<int64_t>(fwd_chain_grid(M), 1)},
+                            x.options().dtype(at::kFloat));
+    tgt_ptr = tgt->data_ptr<float>();
+    dyb_ptr = f.dyb.data_ptr();
+    lp_ptr = f.loss_part.data_ptr<float>();
+  }
+  if (M > 0) {
+    // x pre-swizzled to the same fragment-major layout (per 32-row
+    // m-tile): layer 1's A fragments then come straight from global,
+    // coalesced, and the kernel needs no x LDS tile (occupancy 2 -> 3
+    // workgroups/CU). Pads are zeroed by the swizzle kernel
+    // (uninitialized bf16 could be NaN; NaN * W1pad(0) would poison
+    // real rows).
+    const int64_t Mp = (M + 31) / 32 * 32;
+    auto xs = at::empty({Mp * 112}, x.options());
+    if (xt_out.has_value()) {
+      // one pass over x emits both the forward and the wgrad layouts
+      launch_swizzle_x_both(x.data_ptr(), xs.data_ptr(),
+                            xt_out->data_ptr(), M, pi16 ? 1 : 0,
+                            current_stream());
+    } else {
+      launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
+    }
+    launch_fwd_chain(
+        xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
+        W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
+        b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
+        f.a1t.data_ptr(),
+        reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
+        f.a2t.data_ptr(),
+        reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
+        f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
+        pi16 ? 1 : 0, current_stream());
+  }
+  return f;
+}
+
 std::vector<at::Tensor> fwd_chain_bf16(
     const at::Tensor& x, const at::Tensor& W1, const at::Tensor& b1,
     const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& W3,
@@ -681,68 +756,28 @@ std::vector<at::Tensor> fwd_chain_bf16(
   const int64_t M = x.size(0);
   // The kernel's A-fragment loads need W1's k-dim padded 100 -> 112.
   auto W1p = w1_padded ? W1 : at::constant_pad_nd(W1, {0, 12}).contiguous();
-  // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
-  // 32-bit relu-mask words per column) — the backward chain consumes
-  // masks, the wgrad kernel consumes the fragments; nothing reads
-  // row-major a1/a2.
-  const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
-  const int64_t mchunks = mtiles * 2;
-  auto a1t = at::empty({16 * mchunks * 512}, x.options());
-  auto a2t = at::empty({8 * mchunks * 512}, x.options());
-  auto mask1 = at::empty({mtiles, 512}, x.options().dtype(at::kInt));
-  auto mask2 = at::empty({mtiles, 256}, x.options().dtype(at::kInt));
-  auto a3 = at::empty({M, 128}, x.options());
-  auto out = at::empty({M, 1}, x.options());
   // Fused MSE epilogue: with a target, the kernel also emits the bf16
   // loss gradient dyb = (2/M)(out - target) and per-block squared-error
   // partials (loss = loss_part.sum()/M) — no eager loss/grad kernels.
   const bool with_loss = target.has_value();
-  at::Tensor tgt, dyb, loss_part;
-  const float* tgt_ptr = nullptr;
-  void* dyb_ptr = nullptr;
-  float* lp_ptr = nullptr;
+  at::Tensor tgt;
   if (with_loss) {
     tgt = target->reshape({-1}).to(at::kFloat).contiguous();
     TORCH_CHECK(tgt.numel() == M, "fwd_chain: target size mismatch");
-    dyb = at::empty({M, 1}, x.options());
-    loss_part = at::empty({std::max<int64_t>(fwd_chain_grid(M), 1)},
-                          x.options().dtype(at::kFloat));
-    tgt_ptr = tgt.data_ptr<float>();
-    dyb_ptr = dyb.data_ptr();
-    lp_ptr = loss_part.data_ptr<float>();
   }
+  at::Tensor W1s, W2s, W3s;
   if (M > 0) {
-    auto W1s = swizzle_frag(W1p);
-    auto W2s = swizzle_frag(W2);
-    auto W3s = swizzle_frag(W3);
-    // x pre-swizzled to the same fragment-major layout (per 32-row
-    // m-tile): layer 1's A fragments then come straight from global,
-    // coalesced, and the kernel needs no x LDS tile (occupancy 2 -> 3
-    // workgroups/CU). Pads are zeroed by the swizzle kernel
-    // (uninitialized bf16 could be NaN; NaN * W1pad(0) would poison
-    // real rows).
-    const int64_t Mp = (M + 31) / 32 * 32;
-    auto xs = at::empty({Mp * 112}, x.options());
-    if (xt_out.has_value()) {
-      // one pass over x emits both the forward and the wgrad layouts
-      launch_swizzle_x_both(x.data_ptr(), xs.data_ptr(),
-                            xt_out->data_ptr(), M, pi16 ? 1 : 0,
-                            current_stream());
-    } else {
-      launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
-    }
-    launch_fwd_chain(xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
-                     W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
-                     b3f.data_ptr<float>(), w4.data_ptr(),
-                     b4f.data_ptr<float>(), a1t.data_ptr(),
-                     reinterpret_cast<uint32_t*>(mask1.data_ptr<int32_t>()),
-                     a2t.data_ptr(),
-                     reinterpret_cast<uint32_t*>(mask2.data_ptr<int32_t>()),
-                     a3.data_ptr(), out.data_ptr(), tgt_ptr, dyb_ptr,
-                     lp_ptr, M, pi16 ? 1 : 0, current_stream());
+    W1s = swizzle_frag(W1p);
+    W2s = swizzle_frag(W2);
+    W3s = swizzle_frag(W3);
   }
-  if (with_loss) return {a1t, mask1, a2t, mask2, a3, out, dyb, loss_part};
-  return {a1t, mask1, a2t, mask2, a3, out};
+  auto f = run_fwd_chain(x, W1s, W2s, W3s, w4, b1f, b2f, b3f, b4f,
+                         with_loss ? &tgt : nullptr, xt_out, pi16);
+  if (with_loss) {
+    return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out, f.dyb,
+            f.loss_part};
+  }
+  return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out};
 }
 
 
@@ -759,6 +794,43 @@ static at::Tensor swizzle_frag_T(const at::Tensor& W) {
       .permute({3, 0, 1, 4, 2})
       .contiguous()
       .view({-1});
+}
+
+constexpr int64_t kPartW = 512 + 256 + 128 + 1 + 256;
+// Width padded to a 4-multiple for the float4 slab reduce; the 3 pad
+// columns are never read back.
+constexpr int64_t kPartWPad = (kPartW + 3) / 4 * 4;
+
+// Buffers + launch of the backward chain, shared by bwd_chain_bf16 and
+// fused_step_bf16. W3Ts/W2Ts are the fragment-major transposed weights.
+struct BwdChainOut {
+  at::Tensor dz1t, dz2t, dz3t, db_part;
+};
+
+BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
+                          const at::Tensor& mask1, const at::Tensor& mask2,
+                          const at::Tensor& w4c, const at::Tensor& W3Ts,
+                          const at::Tensor& W2Ts, bool pi16) {
+  BwdChainOut b;
+  const int64_t M = dy.size(0);
+  const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
+  // dz outputs exist only transposed, in wgrad fragment-major layout.
+  const int64_t mchunks = mtiles * 2;
+  b.dz1t = at::empty({16 * mchunks * 512}, dy.options());
+  b.dz2t = at::empty({8 * mchunks * 512}, dy.options());
+  b.dz3t = at::empty({4 * mchunks * 512}, dy.options());
+  const int64_t grid = bwd_chain_grid(M);
+  b.db_part = at::empty({std::max<int64_t>(grid, 1), kPartWPad},
+                        dy.options().dtype(at::kFloat));
+  if (M == 0) b.db_part.zero_();
+  if (M > 0) {
+    launch_bwd_chain(dy.data_ptr(), a3.data_ptr(), mask1.data_ptr(),
+                     mask2.data_ptr(), w4c.data_ptr(), W3Ts.data_ptr(),
+                     W2Ts.data_ptr(), b.dz1t.data_ptr(), b.dz2t.data_ptr(),
+                     b.dz3t.data_ptr(), b.db_part.data_ptr<float>(), M,
+                     pi16 ? 1 : 0, current_stream());
+  }
+  return b;
 }
 
 std::vector<at::Tensor> bwd_chain_bf16(
@@ -803,26 +875,11 @@ std::vector<at::Tensor> bwd_chain_bf16(
                                   : swizzle_frag(W3.contiguous());
   auto W2Ts = (W2.size(0) == 256) ? swizzle_frag_T(W2.contiguous())
                                   : swizzle_frag(W2.contiguous());
-  // dz outputs exist only transposed, in wgrad fragment-major layout.
-  const int64_t mchunks = mtiles * 2;
-  auto dz1t = at::empty({16 * mchunks * 512}, dy.options());
-  auto dz2t = at::empty({8 * mchunks * 512}, dy.options());
-  auto dz3t = at::empty({4 * mchunks * 512}, dy.options());
-  const int64_t grid = bwd_chain_grid(M);
-  constexpr int64_t kPartW = 512 + 256 + 128 + 1 + 256;
-  // Width padded to a 4-multiple for the float4 slab reduce; the 3 pad
-  // columns are never read back.
-  constexpr int64_t kPartWPad = (kPartW + 3) / 4 * 4;
-  auto db_part = at::empty({std::max<int64_t>(grid, 1), kPartWPad},
-                           dy.options().dtype(at::kFloat));
-  if (M == 0) db_part.zero_();
-  if (M > 0) {
-    launch_bwd_chain(dy.data_ptr(), a3.data_ptr(), mask1.data_ptr(),
-                     mask2.data_ptr(), w4c.data_ptr(), W3Ts.data_ptr(),
-                     W2Ts.data_ptr(), dz1t.data_ptr(), dz2t.data_ptr(),
-                     dz3t.data_ptr(), db_part.data_ptr<float>(), M,
-                     pi16 ? 1 : 0, current_stream());
-  }
+  auto bo = run_bwd_chain(dy, a3, mask1, mask2, w4c, W3Ts, W2Ts, pi16);
+  auto& dz1t = bo.dz1t;
+  auto& dz2t = bo.dz2t;
+  auto& dz3t = bo.dz3t;
+  auto& db_part = bo.db_part;
   // Column reduction with the split-slab reduce kernel (the GEMV ran at
   // ~0.9 TB/s; this streams the 28 MB slab near roofline). Pad columns
   // may sum garbage; they are never read.
@@ -840,6 +897,21 @@ std::vector<at::Tensor> bwd_chain_bf16(
           db.narrow(0, 512 + 256, 128),
           db.narrow(0, 512 + 256 + 128, 1),
           dw4};
+}
+
+// Per-slab fp32 partials of one fragment-major wgrad, [nslabs, N*K]:
+// buffer + launch, shared by wgrad_frag_bf16 and fused_step_bf16.
+// Requires mchunks > 0 and a tile config launch_wgrad_frag dispatches.
+at::Tensor run_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT,
+                          int64_t N, int64_t K, int64_t mchunks,
+                          int64_t nt_w, int64_t kt_w) {
+  const int64_t nslabs = wgrad_frag_nslabs(mchunks, (int32_t)N, (int32_t)K,
+                                           (int32_t)nt_w, (int32_t)kt_w);
+  auto part = at::empty({nslabs, N * K}, AT.options().dtype(at::kFloat));
+  launch_wgrad_frag(AT.data_ptr(), BT.data_ptr(), part.data_ptr<float>(),
+                    (int32_t)N, (int32_t)K, mchunks, (int32_t)nt_w,
+                    (int32_t)kt_w, current_stream());
+  return part;
 }
 
 }  // namespace
@@ -883,18 +955,232 @@ at::Tensor wgrad_frag_bf16(const at::Tensor& AT, const at::Tensor& BT,
   if (mchunks > 0) {
     // Per-slab fp32 partials + split-slab reduce (atomic combine over
     // <= a handful of writers per line).
-    const int64_t nslabs = wgrad_frag_nslabs(mchunks, (int32_t)N,
-                                             (int32_t)K, (int32_t)nt_w,
-                                             (int32_t)kt_w);
-    auto part =
-        at::empty({nslabs, N * K}, AT.options().dtype(at::kFloat));
-    launch_wgrad_frag(AT.data_ptr(), BT.data_ptr(), part.data_ptr<float>(),
-                      (int32_t)N, (int32_t)K, mchunks, (int32_t)nt_w,
-                      (int32_t)kt_w, current_stream());
+    auto part = run_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w);
+    const int64_t nslabs = part.size(0);
     launch_slab_reduce(part.data_ptr<float>(), dW.data_ptr<float>(),
                        N * K, nslabs, current_stream());
   }
   return dW;
+}
+
+// ---------------------------------------------------------------------
+// Fused-step glue (csrc/step_glue.hip): one prep launch ahead of the
+// chain kernels, one finalize launch behind the wgrads.
+// ---------------------------------------------------------------------
+namespace {
+
+void check_master(const std::vector<at::Tensor>& w, const char* who) {
+  TORCH_CHECK(w.size() == 4, who, ": weights must be [W1, W2, W3, w4]");
+  const int64_t shp[4][2] = {{512, 100}, {256, 512}, {128, 256}, {1, 128}};
+  for (int i = 0; i < 4; i++) {
+    TORCH_CHECK(w[i].is_cuda() && w[i].scalar_type() == at::kFloat &&
+                    w[i].is_contiguous() &&
+                    w[i].numel() == shp[i][0] * shp[i][1] &&
+                    (i == 3 || (w[i].dim() == 2 && w[i].size(0) == shp[i][0])),
+                who, ": weight ", i, " must be contiguous fp32 [", shp[i][0],
+                ",", shp[i][1], "] on GPU");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(w[i].data_ptr()) % 16 == 0,
+                who, ": weight ", i, " must be 16-byte aligned");
+  }
+}
+
+struct PrepOut {
+  at::Tensor W1s, W2s, W3s, W2Ts, W3Ts, w4b, tgt;
+};
+
+// ``bufs``: optional caller buffers for the six bf16 outputs. ``target``
+// fp32 passes through untouched (no launch work); fp64 is cast in-kernel.
+PrepOut run_step_prep(const std::vector<at::Tensor>& w,
+                      const c10::optional<at::Tensor>& target,
+                      const c10::optional<std::vector<at::Tensor>>& bufs) {
+  check_master(w, "step_prep");
+  const int64_t numel[6] = {512 * 112, 256 * 512, 128 * 256,
+                            256 * 512, 128 * 256, 128};
+  at::Tensor o[6];
+  auto bf = w[0].options().dtype(at::kBFloat16);
+  if (bufs.has_value()) {
+    TORCH_CHECK(bufs->size() == 6, "step_prep: need six output buffers");
+  }
+  for (int i = 0; i < 6; i++) {
+    if (bufs.has_value()) {
+      o[i] = (*bufs)[i];
+      TORCH_CHECK(o[i].is_cuda() && o[i].scalar_type() == at::kBFloat16 &&
+                      o[i].is_contiguous() && o[i].numel() == numel[i] &&
+                      reinterpret_cast<uintptr_t>(o[i].data_ptr()) % 16 == 0,
+                  "step_prep: output buffer ", i,
+                  " must be contiguous aligned bf16 with ", numel[i],
+                  " elements");
+    } else {
+      o[i] = at::empty({numel[i]}, bf);
+    }
+  }
+  PrepOut r{o[0], o[1], o[2], o[3], o[4], o[5], at::Tensor()};
+  StepPrepArgs p{};
+  p.W1 = w[0].data_ptr<float>();
+  p.W2 = w[1].data_ptr<float>();
+  p.W3 = w[2].data_ptr<float>();
+  p.w4 = w[3].data_ptr<float>();
+  p.W1s = reinterpret_cast<uint16_t*>(o[0].data_ptr());
+  p.W2s = reinterpret_cast<uint16_t*>(o[1].data_ptr());
+  p.W3s = reinterpret_cast<uint16_t*>(o[2].data_ptr());
+  p.W2Ts = reinterpret_cast<uint16_t*>(o[3].data_ptr());
+  p.W3Ts = reinterpret_cast<uint16_t*>(o[4].data_ptr());
+  p.w4b = reinterpret_cast<uint16_t*>(o[5].data_ptr());
+  if (target.has_value()) {
+    TORCH_CHECK(target->is_cuda() &&
+                    (target->scalar_type() == at::kFloat ||
+                     target->scalar_type() == at::kDouble),
+                "step_prep: target must be fp32 or fp64 on GPU");
+    auto t = target->reshape({-1}).contiguous();
+    if (t.scalar_type() == at::kDouble) {
+      r.tgt = at::empty({t.numel()}, t.options().dtype(at::kFloat));
+      p.tgt64 = t.data_ptr<double>();
+      p.tgt32 = r.tgt.data_ptr<float>();
+      p.M = t.numel();
+    } else {
+      r.tgt = t;
+    }
+  }
+  launch_step_prep(p, current_stream());
+  return r;
+}
+
+// outs (optional): [dW1, dW2, dW3, dW4, db1, db2, db3, db4] contiguous
+// fp32. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4].
+std::vector<at::Tensor> run_step_finalize(
+    const at::Tensor& part1, const at::Tensor& part2,
+    const at::Tensor& part3, const at::Tensor& db_part,
+    const at::Tensor& loss_part, int64_t M,
+    const c10::optional<std::vector<at::Tensor>>& outs) {
+  auto chk = [](const at::Tensor& t, int64_t w, const char* nm) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                    t.is_contiguous() && t.dim() == 2 && t.size(1) == w &&
+                    t.size(0) >= 1 &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                "step_finalize: ", nm, " must be contiguous fp32 [rows>=1, ",
+                w, "] on GPU");
+  };
+  chk(part1, 512 * 128, "part1");
+  chk(part2, 256 * 512, "part2");
+  chk(part3, 128 * 256, "part3");
+  chk(db_part, kPartWPad, "db_part");
+  TORCH_CHECK(loss_part.is_cuda() && loss_part.scalar_type() == at::kFloat &&
+                  loss_part.is_contiguous(),
+              "step_finalize: loss_part must be contiguous fp32 on GPU");
+  TORCH_CHECK(M >= 1, "step_finalize: M must be positive");
+  const std::vector<std::vector<int64_t>> shp = {
+      {512, 100}, {256, 512}, {128, 256}, {1, 128},
+      {512},      {256},      {128},      {1}};
+  std::vector<at::Tensor> o(8);
+  auto f32 = part1.options();
+  if (outs.has_value()) {
+    TORCH_CHECK(outs->size() == 8, "step_finalize: need eight outputs");
+  }
+  for (int i = 0; i < 8; i++) {
+    if (outs.has_value()) {
+      o[i] = (*outs)[i];
+      int64_t n = 1;
+      for (auto d : shp[i]) n *= d;
+      TORCH_CHECK(o[i].is_cuda() && o[i].scalar_type() == at::kFloat &&
+                      o[i].is_contiguous() && o[i].numel() == n,
+                  "step_finalize: output ", i,
+                  " must be contiguous fp32 with ", n, " elements");
+      TORCH_CHECK(i >= 3 ||
+                      reinterpret_cast<uintptr_t>(o[i].data_ptr()) % 16 == 0,
+                  "step_finalize: output ", i, " must be 16-byte aligned");
+    } else {
+      o[i] = at::empty(shp[i], f32);
+    }
+  }
+  auto loss = at::empty({}, f32);
+  StepFinArgs p{};
+  p.part1 = part1.data_ptr<float>();
+  p.part2 = part2.data_ptr<float>();
+  p.part3 = part3.data_ptr<float>();
+  p.db_part = db_part.data_ptr<float>();
+  p.loss_part = loss_part.data_ptr<float>();
+  p.ns1 = part1.size(0);
+  p.ns2 = part2.size(0);
+  p.ns3 = part3.size(0);
+  p.db_rows = db_part.size(0);
+  p.loss_n = loss_part.numel();
+  p.M = M;
+  p.dw1 = o[0].data_ptr<float>();
+  p.dw2 = o[1].data_ptr<float>();
+  p.dw3 = o[2].data_ptr<float>();
+  p.dw4 = o[3].data_ptr<float>();
+  p.db1 = o[4].data_ptr<float>();
+  p.db2 = o[5].data_ptr<float>();
+  p.db3 = o[6].data_ptr<float>();
+  p.db4 = o[7].data_ptr<float>();
+  p.loss = loss.data_ptr<float>();
+  launch_step_finalize(p, current_stream());
+  return {loss, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
+}
+
+}  // namespace
+
+// [W1s, W2s, W3s, W2Ts, W3Ts, w4 bf16] (+ fp32 target when one is given).
+std::vector<at::Tensor> step_prep(
+    const std::vector<at::Tensor>& weights,
+    const c10::optional<at::Tensor>& target,
+    const c10::optional<std::vector<at::Tensor>>& outs) {
+  auto r = run_step_prep(weights, target, outs);
+  std::vector<at::Tensor> v = {r.W1s, r.W2s, r.W3s, r.W2Ts, r.W3Ts, r.w4b};
+  if (target.has_value()) v.push_back(r.tgt);
+  return v;
+}
+
+std::vector<at::Tensor> step_finalize(
+    const at::Tensor& part1, const at::Tensor& part2,
+    const at::Tensor& part3, const at::Tensor& db_part,
+    const at::Tensor& loss_part, int64_t M,
+    const c10::optional<std::vector<at::Tensor>>& outs) {
+  return run_step_finalize(part1, part2, part3, db_part, loss_part, M, outs);
+}
+
+// The whole fused train step of the stock TabularMLP(100-512-256-128-1)
+// in 8 launches: prep -> x swizzle -> fwd chain -> bwd chain -> three
+// fragment wgrads into slab partials -> finalize. fp32 master
+// ``weights`` [W1, W2, W3, w4] and ``biases`` [b1..b4] are read
+// directly. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4];
+// with ``outs`` the eight gradients are written into the caller's
+// tensors (same order). No sync, no host read: graph-capture safe.
+std::vector<at::Tensor> fused_step_bf16(
+    const at::Tensor& x, const at::Tensor& target,
+    const std::vector<at::Tensor>& weights,
+    const std::vector<at::Tensor>& biases, bool pi16,
+    const c10::optional<std::vector<at::Tensor>>& outs) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
+              "fused_step: x must be contiguous bf16 [M,100]");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(M > 0, "fused_step: empty batch");
+  TORCH_CHECK(target.numel() == M, "fused_step: target size mismatch");
+  TORCH_CHECK(biases.size() == 4, "fused_step: biases must be [b1..b4]");
+  const int64_t bn[4] = {512, 256, 128, 1};
+  for (int i = 0; i < 4; i++) {
+    TORCH_CHECK(biases[i].is_cuda() &&
+                    biases[i].scalar_type() == at::kFloat &&
+                    biases[i].is_contiguous() && biases[i].numel() == bn[i],
+                "fused_step: bias ", i, " must be contiguous fp32 [", bn[i],
+                "] on GPU");
+  }
+  auto pr = run_step_prep(weights, target, c10::nullopt);
+  const int64_t mchunks = 2 * ((M + 31) / 32);
+  c10::optional<at::Tensor> xt =
+      at::empty({4 * mchunks * 512}, x.options());
+  auto f = run_fwd_chain(x, pr.W1s, pr.W2s, pr.W3s, pr.w4b, biases[0],
+                         biases[1], biases[2], biases[3], &pr.tgt, xt, pi16);
+  auto b = run_bwd_chain(f.dyb, f.a3, f.mask1, f.mask2, pr.w4b, pr.W3Ts,
+                         pr.W2Ts, pi16);
+  // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
+  const char* st = std::getenv("RSDL_WGRAD_SMALL_TILES");
+  const int64_t kt23 = (st != nullptr && std::strcmp(st, "1") == 0) ? 4 : 8;
+  auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4);
+  auto p2 = run_wgrad_frag(b.dz2t, f.a1t, 256, 512, mchunks, 1, kt23);
+  auto p3 = run_wgrad_frag(b.dz3t, f.a2t, 128, 256, mchunks, 1, kt23);
+  return run_step_finalize(p1, p2, p3, b.db_part, f.loss_part, M, outs);
 }
 
 }  // namespace rsdl
@@ -940,6 +1226,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bwd_chain_bf16", &rsdl::bwd_chain_bf16, py::arg("dy"),
         py::arg("a3"), py::arg("mask1"), py::arg("mask2"), py::arg("w4"),
         py::arg("W3"), py::arg("W2"), py::arg("pi16") = false);
+  m.def("step_prep", &rsdl::step_prep, py::arg("weights"),
+        py::arg("target") = c10::nullopt, py::arg("outs") = c10::nullopt);
+  m.def("step_finalize", &rsdl::step_finalize, py::arg("part1"),
+        py::arg("part2"), py::arg("part3"), py::arg("db_part"),
+        py::arg("loss_part"), py::arg("M"), py::arg("outs") = c10::nullopt);
+  m.def("fused_step_bf16", &rsdl::fused_step_bf16, py::arg("x"),
+        py::arg("target"), py::arg("weights"), py::arg("biases"),
+        py::arg("pi16") = false, py::arg("outs") = c10::nullopt);
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

@@ -1,12 +1,22 @@
 """Fused train step for the fixed TabularMLP(100-512-256-128-1) — the
 DEFAULT bench step (RSDL_FUSED_STEP=0 reverts to eager autocast).
 
-No autograd graph; the step IS the schedule (~12 launches):
-  x swizzle (emits both x layouts) -> fwd chain (3 MFMA layers + head +
-  MSE loss/grad; emits a1^T/a2^T wgrad fragments + relu-mask words) ->
-  bwd chain (dgrad chain from mask bits; emits dz^T fragments + db/dW4
-  partials) -> 3 fragment-major wgrad kernels -> slab-partial reduces ->
-  optimizer.
+No autograd graph; the step IS the schedule. On the default native path
+(hip.fused_step_bf16, one extension call) it is 8 launches, no memset
+and no copy:
+  1. step_prep: fp32 master weights -> bf16 fragment-major W1s (K padded
+     to 112), W2s, W3s, W2^T s, W3^T s, bf16 w4, fp32 target
+  2. x swizzle (emits both x layouts)
+  3. fwd chain (3 MFMA layers + head + MSE loss/grad; emits a1^T/a2^T
+     wgrad fragments + relu-mask words)
+  4. bwd chain (dgrad chain from mask bits; emits dz^T fragments + db/dW4
+     partials)
+  5-7. three fragment-major wgrad kernels into per-slab partials
+  8. step_finalize: all partials -> dW1 [512,100], dW2, dW3, dW4, db1..4
+     and the scalar loss, fixed summation order, written in place
+then the optimizer. The composed path (FakeHip CPU mirror, grad_hook
+staging, _NATIVE_GLUE off) runs the same heavy kernels through the three
+older bindings with torch ops as glue (~28 launches).
 Activations a1/a2 and gradients dz never exist in row-major form: the
 producers emit the transposed fragment layout the wgrad kernel reads
 (csrc/fwd_chain.hip, csrc/bwd_chain.hip, csrc/wgrad_frag.hip), and the
@@ -31,6 +41,12 @@ from ray_shuffling_data_loader_amd.models.mlp import TabularMLP
 # dim of every consumer); schedule evidence in profiles/r02. Tests may
 # override via fused_step._PI16.
 _PI16 = os.environ.get("RSDL_PI16", "0") == "1"
+
+# Native glue (default on; RSDL_NATIVE_GLUE=0 or fused_step._NATIVE_GLUE =
+# False forces the composed path): the whole schedule runs inside one
+# extension call, hip.fused_step_bf16, with the weight staging and the
+# partial reductions in two kernels of csrc/step_glue.hip.
+_NATIVE_GLUE = os.environ.get("RSDL_NATIVE_GLUE", "1") != "0"
 
 
 def _layers(model: TabularMLP):
@@ -72,6 +88,39 @@ def _weight_buffers(model: TabularMLP, lin):
     return buf
 
 
+def _native_ok(hip, lin, x, target, grad_hook) -> bool:
+    """Whether this call can take hip.fused_step_bf16: the extension has
+    it, no staged grad_hook, and the stock fp32 model plus a bf16 batch
+    sit on a GPU in the layouts the kernels read."""
+    if not (_NATIVE_GLUE and grad_hook is None
+            and hasattr(hip, "fused_step_bf16")):
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
+            and x.shape[0] > 0 and x.is_contiguous()):
+        return False
+    if not (target.is_cuda and target.numel() == x.shape[0]
+            and target.dtype in (torch.float32, torch.float64)):
+        return False
+    return all(
+        p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+        and p.data_ptr() % 16 == 0
+        for m in lin for p in (m.weight, m.bias)
+    )
+
+
+def _flat_outs(lin):
+    """The pre-created .grad views (flat-grad DP mode) in the order
+    hip.fused_step_bf16 writes them, or None if any cannot be written in
+    place (missing, not fp32/contiguous, weight view not 16-B aligned)."""
+    outs = [m.weight.grad for m in lin] + [m.bias.grad for m in lin]
+    for i, g in enumerate(outs):
+        if g is None or g.dtype != torch.float32 or not g.is_contiguous():
+            return None
+        if i < 3 and g.data_ptr() % 16 != 0:
+            return None
+    return outs
+
+
 def fused_step(
     model: TabularMLP, x: torch.Tensor, target: torch.Tensor,
     grad_hook=None,
@@ -93,6 +142,24 @@ def fused_step(
     lin = _layers(model)
     M = x.shape[0]
     from ray_shuffling_data_loader_amd.ops.shuffle_ops import wgrad_frag
+
+    if _native_ok(hip, lin, x, target, grad_hook):
+        flat_mode = getattr(model, "_rsdl_flat_grads", False)
+        outs = _flat_outs(lin) if flat_mode else None
+        if not flat_mode or outs is not None:
+            res = hip.fused_step_bf16(
+                x, target,
+                [m.weight.detach() for m in lin],
+                [m.bias.detach() for m in lin],
+                pi16=_PI16, outs=outs,
+            )
+            if outs is None:
+                # dW1..dW4 then db1..db4, fresh fp32 tensors in the
+                # parameters' shapes.
+                for i, m in enumerate(lin):
+                    m.weight.grad = res[1 + i]
+                    m.bias.grad = res[5 + i]
+            return res[0]
 
     buf = _weight_buffers(model, lin)
     b1, b2, b3, b4 = (m.bias.detach() for m in lin)

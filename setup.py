@@ -46,6 +46,7 @@ try:
         "csrc/bwd_chain.hip",
         "csrc/wgrad_wide.hip",
         "csrc/wgrad_frag.hip",
+        "csrc/step_glue.hip",
     ]
     if all(os.path.exists(s) for s in hip_sources):
         ext_modules.append(
