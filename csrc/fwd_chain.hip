@@ -7,19 +7,35 @@
 //   a3 = relu(a2 @ W3^T + b3)   -> [M,128]
 //   out = a3 @ w4^T + b4        -> [M,1]
 //
-// One 256-thread workgroup carries an FC_MT-row slab through the whole
-// chain: the slab's activations live in LDS between layers, weights are
-// read from global (L2-resident, ~0.44 MB total) per MFMA step, and only
-// x0 (read) and the a1/a2/a3/out tiles (written once for backward) touch
-// HBM. Eliminates the inter-layer activation re-reads of the eager path
+// One workgroup carries a slab of rows through the whole chain: the
+// slab's activations live in LDS between layers, weights are read from
+// global (L2-resident, ~0.44 MB total) per MFMA step, and only x0 (read)
+// and the a1/a2/a3/out tiles (written once for backward) touch HBM.
+// Eliminates the inter-layer activation re-reads of the eager path
 // (~448 MB/step at the bench shape; measured eager fwd 0.25 ms vs a
 // ~0.1 ms fused roofline).
 //
-// FC_MT = 32 (round-2 tuning): the 64-row variant used ~133 KB LDS ->
-// 1 workgroup/CU = 1 wave/SIMD, leaving the L2 weight-fragment latency
-// of the k-loops unhidden even with software pipelining (measured
-// 512 us vs the ~100 us roofline). 32-row tiles take ~67 KB -> 2
-// workgroups/CU, so one workgroup's MFMAs cover the other's loads.
+// Slab size (template MT = 32-row m-tiles per workgroup, `rows` = 32 or
+// 64 per call, default 64; profiles/PERF.md "Round 4"). Every workgroup
+// pulls the whole weight set through the vector-memory path: 442 KB (W1
+// with K padded to 112, W2, W3), once per slab. At M = 250k with 32-row
+// slabs that is 7813 x 442 KB = 3.45 GB per launch (measured: 3.50 GB
+// of L1->L2 read requests, x included) — ~100 us at the chip's ~34.5
+// TB/s aggregate L2 rate, on the path the activation streams use too,
+// and the reason the 32-row kernel sat at 232 us with HBM (~115 us) and
+// MFMA/VALU issue (45-90 us) both far from their limits. A 64-row
+// workgroup (8 waves) gives every wave N/8 columns of BOTH m-tiles in
+// layers 1 and 2, so each B fragment, once in registers, feeds two
+// MFMAs: 1.85 GB measured, 191 us. Layer 3 has only four n-tiles and
+// stays unshared (wave w: m-tile w >> 2, n-tile w & 3; 15 % of the
+// weight bytes). Results are bit-identical between the slab sizes except
+// for the grouping of loss_part (one entry per workgroup).
+// Occupancy decides whether this pays: 64 rows with t1 + t2 side by side
+// (100 KB, or round 2's 133 KB with an x tile) means one workgroup per
+// CU, every barrier spanning the CU — round 2 measured that at 512 us.
+// Here t2 and t3 alias t1 (66.8 KB) and the kernel is held to 128
+// registers, so two 8-wave workgroups share a CU (4 waves/SIMD, against
+// 3 for the 32-row kernel at 50 KB and 140 registers).
 //
 // MFMA orientation (v_mfma_f32_32x32x16_bf16, probe-verified maps in
 // tools/mfma_probe.hip / csrc/wgrad_kernel.hip):
@@ -40,8 +56,9 @@
 // the swizzle per call (weights are 0.44 MB total; a few us).
 //
 // Validated by tests/test_gpu_kernels.py (chain numerics, layout
-// oracles, whole-step parity) and tests/test_chain_sim.py (lane-level
-// index simulation).
+// oracles, whole-step parity), tests/test_chain_rows64_gpu.py (64-row
+// slabs bit-equal to 32-row ones, odd tile counts, regrouped partials)
+// and tests/test_chain_sim.py (lane-level index simulation).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -93,8 +110,7 @@ __device__ __forceinline__ uint32_t fc_cvt_pk_bf16(fc_f32x2 v) {
   return p;
 }
 
-#define FC_MT 32            // rows per workgroup slab
-#define FC_MTILES (FC_MT / 32)  // 32-row MFMA m-tiles per slab
+#define FC_MT 32            // rows per MFMA m-tile (and per x/mask block)
 #define FC_K0 100           // input feature count
 #define FC_K0P 112          // padded to a 16-multiple for the k-loop
 #define FC_N1 512
@@ -118,15 +134,21 @@ __device__ __forceinline__ short fc_f2b(float f) {
   return *reinterpret_cast<short*>(&h);
 }
 
-// One GEMM layer of the chain: src LDS tile [FC_MT][K] (stride SRC_S
-// halfwords) x W[N][K] global -> relu(.+bias) -> dst LDS tile (stride
-// DST_S). N_WAVE = output columns per wave (N/4). Each wave owns m-tiles
-// {0,32} x its n-range; accumulators are static f32x16 arrays.
+// One GEMM layer of the chain for one wave: src tile [MT*32][K] (LDS,
+// stride SRC_S halfwords) x W[N][K] global -> relu(.+bias) -> dst LDS
+// tile (stride DST_S). The wave owns MPW consecutive m-tiles starting at
+// mt0 and NT consecutive n-tiles starting at ntile0; each B (weight)
+// fragment is loaded ONCE and issued against all MPW m-tiles' A
+// fragments, so a 64-row workgroup (MPW = 2) pulls every weight byte
+// through the vector-memory path once per 64 rows instead of once per
+// 32. Each (m-tile, n-tile) accumulator sees the same MFMAs in the same
+// k order whatever MPW is, so the results are bit-identical between the
+// slab sizes.
 // A_FRAGMAJOR: src is a GLOBAL fragment-major m-tile block (layout as
 // the swizzled weights: [kc][h][ml][8], 512 halfwords per k-chunk) —
 // used for layer 1, whose input x is pre-swizzled host-side; SRC_S is
 // ignored. Otherwise src is the LDS tile of the previous layer.
-// EMIT_T: besides the LDS tile, the epilogue emits this m-tile's
+// EMIT_T: besides the LDS tile, the epilogue emits each m-tile's
 // activations TRANSPOSED in wgrad fragment-major layout
 // ([N/32][mchunks][2][32][8]; see csrc/wgrad_frag.hip) plus one 32-bit
 // relu-mask word per column (maskT[m_tile][n], bit i = row i alive) —
@@ -134,47 +156,55 @@ __device__ __forceinline__ short fc_f2b(float f) {
 // only) and the wgrad kernel gets coalesced B fragments for free.
 // Lanes l/l+32 hold complementary 4-row runs of a column; one shfl_xor
 // per 4 values assembles the 8-row fragment runs in registers.
-template <int K, int N, int SRC_S, int DST_S, bool RELU,
-          bool A_FRAGMAJOR = false, bool EMIT_T = false, bool PI16 = false>
-__device__ void fc_layer(const short* __restrict__ src_lds,
-                         const short* __restrict__ W,
-                         const float* __restrict__ bias,
-                         short* __restrict__ dst_lds, int32_t wave,
-                         int32_t lane, short* __restrict__ at_out = nullptr,
-                         uint32_t* __restrict__ mask_row = nullptr,
-                         int64_t mchunks = 0, int64_t mc0 = 0) {
-  constexpr int NT = N / 128;  // n-tiles of 32 per wave (4 waves)
+// has2 (workgroup-uniform, MPW = 2 only): the slab's second m-tile
+// exists. When it does not (odd tile count, last workgroup) its x block,
+// mask rows and fragment chunks lie past the allocations: the A loads
+// then re-read tile 0 and the global emissions are skipped, under this
+// one uniform flag — no per-element guards in the loops.
+// SYNC_EPI: a workgroup barrier between the k-loop and the epilogue, for
+// a dst tile that aliases the src tile.
+template <int K, int N, int MPW, int NT, int SRC_S, int DST_S, bool RELU,
+          bool A_FRAGMAJOR = false, bool EMIT_T = false, bool PI16 = false,
+          bool SYNC_EPI = false>
+__device__ void fc_layer(
+    const short* __restrict__ src_lds, const short* __restrict__ W,
+    const float* __restrict__ bias, short* __restrict__ dst_lds,
+    int32_t mt0, int32_t ntile0, int32_t lane, bool has2,
+    short* __restrict__ at_out = nullptr,
+    uint32_t* __restrict__ mask_row = nullptr, int64_t mchunks = 0,
+    int64_t mc0 = 0) {
   constexpr int ITERS = K / 16;
-  const int32_t n_base = wave * (N / 4);
+  const int32_t n_base = ntile0 * 32;
   const int32_t frag_k0 = (lane >> 5) * 8;
   const int32_t ml = lane & 31;  // A row within m-tile / D col (n)
 
-  // Software-pipelined k-loop: LDS occupancy pins this kernel at 1
-  // wave/SIMD, so cross-wave latency hiding does not exist — the next
+  // Software-pipelined k-loop: LDS occupancy holds this kernel to 3-4
+  // waves/SIMD, so cross-wave latency hiding is thin — the next
   // iteration's A (LDS) and B (global/L2) fragments must be IN FLIGHT
   // while the current MFMAs run. Fully unrolled (compile-time ITERS)
   // double-buffered prefetch: buf indices become constants after unroll,
   // so the fragment arrays stay in registers.
-  const short* srcA[FC_MTILES];
+  const short* srcA[MPW];
   #pragma unroll
-  for (int mt = 0; mt < FC_MTILES; mt++) {
+  for (int mt = 0; mt < MPW; mt++) {
+    const int32_t tile = mt0 + ((mt == 0 || has2) ? mt : 0);
     srcA[mt] = A_FRAGMAJOR
-                   ? &src_lds[(int64_t)mt * ITERS * 512 + lane * 8]
-                   : &src_lds[(mt * 32 + ml) * SRC_S + frag_k0];
+                   ? &src_lds[(int64_t)tile * ITERS * 512 + lane * 8]
+                   : &src_lds[((mt0 + mt) * 32 + ml) * SRC_S + frag_k0];
   }
   // Swizzled weight base for this wave's n-tiles: block (ntile, kc) is
   // 512 contiguous halfwords; lane's 16-B slice at lane*8.
   const short* srcB[NT];
   #pragma unroll
   for (int nt = 0; nt < NT; nt++) {
-    srcB[nt] = &W[((int64_t)(wave * NT + nt) * ITERS) * 512 + lane * 8];
+    srcB[nt] = &W[((int64_t)(ntile0 + nt) * ITERS) * 512 + lane * 8];
   }
 
-  fc_f32x16 acc[FC_MTILES][NT] = {};
-  fc_bf16x8 a[2][FC_MTILES], b[2][NT];
+  fc_f32x16 acc[MPW][NT] = {};
+  fc_bf16x8 a[2][MPW], b[2][NT];
 
   #pragma unroll
-  for (int mt = 0; mt < FC_MTILES; mt++) {
+  for (int mt = 0; mt < MPW; mt++) {
     *reinterpret_cast<uint4*>(&a[0][mt]) =
         *reinterpret_cast<const uint4*>(srcA[mt]);
   }
@@ -190,7 +220,7 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
     if (i + 1 < ITERS) {
       const int32_t k = (i + 1) * 16;
       #pragma unroll
-      for (int mt = 0; mt < FC_MTILES; mt++) {
+      for (int mt = 0; mt < MPW; mt++) {
         *reinterpret_cast<uint4*>(&a[nxt][mt]) =
             *reinterpret_cast<const uint4*>(
                 &srcA[mt][A_FRAGMAJOR ? (i + 1) * 512 : k]);
@@ -202,7 +232,7 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
       }
     }
     #pragma unroll
-    for (int mt = 0; mt < FC_MTILES; mt++) {
+    for (int mt = 0; mt < MPW; mt++) {
       #pragma unroll
       for (int nt = 0; nt < NT; nt++) {
         acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -216,10 +246,10 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
   // All arithmetic runs on packed row pairs (v_pk_add/max_f32 +
   // v_cvt_pk_bf16_f32): regs 2q/2q+1 are consecutive rows, and the
   // packed bf16 word IS the emission payload.
-  static_assert(!EMIT_T || FC_MTILES == 1, "EMIT_T assumes 32-row slabs");
+  if (SYNC_EPI) __syncthreads();
   const int32_t h = lane >> 5;
   #pragma unroll
-  for (int mt = 0; mt < FC_MTILES; mt++) {
+  for (int mt = 0; mt < MPW; mt++) {
     #pragma unroll
     for (int nt = 0; nt < NT; nt++) {
       const int32_t n = n_base + nt * 32 + ml;
@@ -227,7 +257,7 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
       // One base address per column; row offsets are compile-time, so
       // the b16 stores use ds_write immediate offsets instead of ~1.5
       // VALU address ops each.
-      short* colbase = dst_lds + (mt * 32 + 4 * h) * DST_S + n;
+      short* colbase = dst_lds + ((mt0 + mt) * 32 + 4 * h) * DST_S + n;
       uint32_t p[8];
       #pragma unroll
       for (int q = 0; q < 8; q++) {
@@ -240,7 +270,7 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
         colbase[roff] = (short)(pk & 0xFFFFu);
         colbase[roff + DST_S] = (short)(pk >> 16);
       }
-      if (EMIT_T) {
+      if (EMIT_T && (mt == 0 || has2)) {
         // Mask word for column n (bit i = bf16 value of row i > 0): a
         // positive nonzero bf16 is 0 < bits < 0x8000.
         uint32_t w = 0;
@@ -285,28 +315,29 @@ __device__ void fc_layer(const short* __restrict__ src_lds,
           run1[3] = h == 0 ? rx[3] : p[7];
         }
         const int64_t nt_g = (int64_t)(n_base + nt * 32) >> 5;
-        short* blk0 = at_out + ((nt_g * mchunks + mc0) * 512) + h * 256 +
+        const int64_t mc = mc0 + 2 * (mt0 + mt);
+        short* blk0 = at_out + ((nt_g * mchunks + mc) * 512) + h * 256 +
                       ml * 8;
-        short* blk1 = at_out + ((nt_g * mchunks + mc0 + 1) * 512) +
+        short* blk1 = at_out + ((nt_g * mchunks + mc + 1) * 512) +
                       h * 256 + ml * 8;
         _rsdl_store(run0,
                                     reinterpret_cast<fc_u32x4*>(blk0));
         _rsdl_store(run1,
                                     reinterpret_cast<fc_u32x4*>(blk1));
         w |= __shfl_xor(w, 32);
-        if (h == 0) mask_row[n] = w;
+        if (h == 0) mask_row[(mt0 + mt) * N + n] = w;
       }
     }
   }
 }
 
-// Copy an LDS activation tile [FC_MT][N] (stride S halfwords) to the
+// Copy an LDS activation tile [MT*32][N] (stride S halfwords) to the
 // global row-major [M, N] tensor, vectorized 16 B.
-template <int N, int S>
+template <int MT, int N, int S>
 __device__ void fc_store_tile(const short* __restrict__ lds, short* out,
                               int64_t m0, int64_t M, int32_t tid) {
   constexpr int VPR = N / 8;  // uint4 vectors per row
-  for (int32_t u = tid; u < FC_MT * VPR; u += 256) {
+  for (int32_t u = tid; u < MT * FC_MT * VPR; u += 256 * MT) {
     const int32_t m = u / VPR;
     const int32_t c = (u % VPR) * 8;
     if (m0 + m < M) {
@@ -320,8 +351,23 @@ __device__ void fc_store_tile(const short* __restrict__ lds, short* out,
   }
 }
 
-template <bool PI16 = false>
-__global__ void __launch_bounds__(256) fwd_chain_kernel(
+// The 64-row kernels run at exactly 128 registers. Handing each layer an
+// opaque copy of the lane index keeps the compiler from carrying lane-
+// derived address terms across a whole layer (it spilled one to scratch
+// rather than recompute a shift); no-op at MT = 1.
+template <int MT>
+__device__ __forceinline__ int32_t fc_fresh_lane(int32_t lane) {
+  if (MT == 2) asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// MT = 32-row m-tiles per workgroup slab (1 or 2); 256 * MT threads. See
+// the header for the slab-size reasoning. The second __launch_bounds__
+// figure is waves per SIMD: the 64-row kernel must fit 128 registers so
+// that two 8-wave workgroups share a CU.
+template <int MT, bool PI16>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+fwd_chain_kernel(
     const short* __restrict__ x0s,  // fragment-major swizzled x (see note)
     const short* __restrict__ W1, const float* __restrict__ b1,
     const short* __restrict__ W2, const float* __restrict__ b2,
@@ -339,40 +385,58 @@ __global__ void __launch_bounds__(256) fwd_chain_kernel(
     const float* __restrict__ target, short* __restrict__ dyb,
     float* __restrict__ loss_part, float inv_m, int64_t M,
     int64_t mchunks) {
-  // LDS budget is the occupancy lever: t1 + t2 + lsum = ~50 KB -> 3
-  // workgroups/CU. x needs no tile (pre-swizzled fragment-major in
-  // global, coalesced A loads), and t3 ALIASES t1's storage — layer 3
-  // runs after layer 2 consumed t1 (a1 itself leaves through the
-  // EMIT_T epilogue, transposed, plus mask words — no row-major a1/a2
-  // tensors exist at all).
-  __shared__ __align__(16) char smem[FC_MT * FC_S1 * 2 + FC_MT * FC_S2 * 2 +
-                                     FC_MT * 4];
+  // LDS budget is the occupancy lever. x needs no tile (pre-swizzled
+  // fragment-major in global, coalesced A loads), and a1 itself leaves
+  // through the EMIT_T epilogue, transposed, plus mask words — no
+  // row-major a1/a2 tensors exist at all.
+  //   MT = 1: t1 + t2 + lsum = ~50 KB -> 3 workgroups/CU; t3 ALIASES t1
+  //           (layer 3 runs after layer 2 consumed t1).
+  //   MT = 2: t1 + t2 would be 100 KB = one workgroup/CU. t2 ALIASES t1
+  //           too (layer 2 puts a barrier between its k-loop, the last
+  //           reader of t1, and its epilogue) and t3 sits behind t2
+  //           inside t1's storage: 66.8 KB -> 2 workgroups/CU.
+  constexpr int ROWS = MT * FC_MT;
+  constexpr int T1B = ROWS * FC_S1 * 2;
+  constexpr int T2B = ROWS * FC_S2 * 2;
+  constexpr int TILEB = MT == 1 ? T1B + T2B : T1B;
+  static_assert(MT == 1 || T2B + ROWS * FC_S3 * 2 <= T1B, "t2+t3 in t1");
+  __shared__ __align__(16) char smem[TILEB + ROWS * 4];
   short* t1 = reinterpret_cast<short*>(smem);
-  short* t2 = reinterpret_cast<short*>(smem + FC_MT * FC_S1 * 2);
-  short* t3 = t1;  // aliased: live ranges are disjoint (barrier-ordered)
-  float* lsum = reinterpret_cast<float*>(smem + FC_MT * FC_S1 * 2 +
-                                         FC_MT * FC_S2 * 2);
+  short* t2 = reinterpret_cast<short*>(MT == 1 ? smem + T1B : smem);
+  // aliased: live ranges are disjoint (barrier-ordered)
+  short* t3 = reinterpret_cast<short*>(MT == 1 ? smem : smem + T2B);
+  float* lsum = reinterpret_cast<float*>(smem + TILEB);
 
-  const int64_t m0 = (int64_t)blockIdx.x * FC_MT;
+  const int64_t m0 = (int64_t)blockIdx.x * ROWS;
   const int32_t tid = threadIdx.x;
   const int32_t wave = tid >> 6;
   const int32_t lane = tid & 63;
-  const int64_t mc0 = (int64_t)blockIdx.x * 2;
+  const int64_t mt_g0 = (int64_t)blockIdx.x * MT;  // first global m-tile
+  const int64_t mc0 = mt_g0 * 2;
+  // Workgroup-uniform: the slab's second m-tile exists (see fc_layer).
+  const bool has2 = MT == 1 || 2 * (mt_g0 + 1) < mchunks;
 
+  // Layers 1 and 2: every wave takes N/(4*MT) columns of all MT m-tiles,
+  // so each weight fragment it loads feeds MT MFMAs.
   // Layer 1: A fragments straight from the swizzled global x block.
-  const short* xblk = &x0s[(int64_t)blockIdx.x * (FC_K0P / 16) * 512];
-  fc_layer<FC_K0P, FC_N1, 0, FC_S1, true, true, true, PI16>(
-      xblk, W1, b1, t1, wave, lane, a1t, &mask1[(int64_t)blockIdx.x * FC_N1],
-      mchunks, mc0);
+  const short* xblk = &x0s[mt_g0 * (FC_K0P / 16) * 512];
+  constexpr int NT1 = FC_N1 / (128 * MT), NT2 = FC_N2 / (128 * MT);
+  fc_layer<FC_K0P, FC_N1, MT, NT1, 0, FC_S1, true, true, true, PI16>(
+      xblk, W1, b1, t1, 0, wave * NT1, fc_fresh_lane<MT>(lane), has2, a1t,
+      &mask1[mt_g0 * FC_N1], mchunks, mc0);
   __syncthreads();
-  fc_layer<FC_N1, FC_N2, FC_S1, FC_S2, true, false, true, PI16>(
-      t1, W2, b2, t2, wave, lane, a2t, &mask2[(int64_t)blockIdx.x * FC_N2],
-      mchunks, mc0);
+  fc_layer<FC_N1, FC_N2, MT, NT2, FC_S1, FC_S2, true, false, true, PI16,
+           MT == 2>(
+      t1, W2, b2, t2, 0, wave * NT2, fc_fresh_lane<MT>(lane), has2, a2t,
+      &mask2[mt_g0 * FC_N2], mchunks, mc0);
   __syncthreads();
-  fc_layer<FC_N2, FC_N3, FC_S2, FC_S3, true>(t2, W3, b3, t3, wave, lane);
+  // Layer 3 has only four n-tiles: wave w takes (m-tile w >> 2, n-tile
+  // w & 3), unshared (15 % of the weight bytes).
+  fc_layer<FC_N2, FC_N3, 1, 1, FC_S2, FC_S3, true>(
+      t2, W3, b3, t3, wave >> 2, wave & 3, fc_fresh_lane<MT>(lane), true);
   __syncthreads();
 
-  // Head: out[m] = sum_k a3[m,k] * w4[k] + b4. 256/FC_MT threads per row,
+  // Head: out[m] = sum_k a3[m,k] * w4[k] + b4. 8 threads per row,
   // pair-wise LDS-free reduce via wave shuffles (partners are adjacent
   // lanes).
   {
@@ -409,12 +473,12 @@ __global__ void __launch_bounds__(256) fwd_chain_kernel(
     if (tid == 0) {
       float s = 0.f;
       #pragma unroll
-      for (int32_t m = 0; m < FC_MT; m++) s += lsum[m];
+      for (int32_t m = 0; m < ROWS; m++) s += lsum[m];
       loss_part[blockIdx.x] = s;
     }
   }
 
-  fc_store_tile<FC_N3, FC_S3>(t3, a3, m0, M, tid);
+  fc_store_tile<MT, FC_N3, FC_S3>(t3, a3, m0, M, tid);
 }
 
 // x [M,100] bf16 -> fragment-major [ceil(M/32)][7][2][32][8] with zero
@@ -598,7 +662,10 @@ void launch_swizzle_xt(const void* x, void* out, int64_t M, int pi16,
                      reinterpret_cast<short*>(out), M, total);
 }
 
-int64_t fwd_chain_grid(int64_t M) { return (M + FC_MT - 1) / FC_MT; }
+// rows = rows per workgroup slab, 32 or 64 (validated by the binding).
+int64_t fwd_chain_grid(int64_t M, int rows) {
+  return (M + rows - 1) / rows;
+}
 
 void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       const void* W2, const float* b2, const void* W3,
@@ -606,11 +673,15 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       void* a1t, uint32_t* mask1, void* a2t,
                       uint32_t* mask2, void* a3, void* out,
                       const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, hipStream_t stream) {
-  const int32_t grid = (int32_t)((M + FC_MT - 1) / FC_MT);
-  const int64_t mchunks = (int64_t)grid * 2;
-  auto kern = pi16 ? fwd_chain_kernel<true> : fwd_chain_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                      int64_t M, int pi16, int rows, hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
+  // The global layouts are per 32-row m-tile whatever the slab size.
+  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
+  auto kern = rows == 64
+      ? (pi16 ? fwd_chain_kernel<2, true> : fwd_chain_kernel<2, false>)
+      : (pi16 ? fwd_chain_kernel<1, true> : fwd_chain_kernel<1, false>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+                     stream,
                      reinterpret_cast<const short*>(x0s),
                      reinterpret_cast<const short*>(W1), b1,
                      reinterpret_cast<const short*>(W2), b2,

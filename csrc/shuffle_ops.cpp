@@ -99,7 +99,7 @@ void launch_wgrad_wide(const void* dy, const void* x, float* dW, float* db,
 void launch_relu_bwd_bias(const void* dy, const void* y, void* dx,
                           float* db_part, int64_t nvec, int32_t N,
                           int32_t grid, hipStream_t stream);
-int64_t fwd_chain_grid(int64_t M);
+int64_t fwd_chain_grid(int64_t M, int rows);
 void launch_swizzle_x(const void* x, void* out, int64_t M,
                       hipStream_t stream);
 void launch_swizzle_xt(const void* x, void* out, int64_t M, int pi16,
@@ -112,8 +112,8 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       void* a1t, uint32_t* mask1, void* a2t,
                       uint32_t* mask2, void* a3, void* out,
                       const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, hipStream_t stream);
-int64_t bwd_chain_grid(int64_t M);
+                      int64_t M, int pi16, int rows, hipStream_t stream);
+int64_t bwd_chain_grid(int64_t M, int rows);
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
                        int32_t kt_w, hipStream_t stream);
@@ -124,7 +124,7 @@ void launch_slab_reduce(const float* part, float* out, int64_t nk,
 void launch_bwd_chain(const void* dy, const void* a3, const void* mask1,
                       const void* mask2, const void* w4, const void* W3T,
                       const void* W2T, void* dz1t, void* dz2t, void* dz3t,
-                      float* db_part, int64_t M, int pi16,
+                      float* db_part, int64_t M, int pi16, int rows,
                       hipStream_t stream);
 
 namespace {
@@ -650,6 +650,30 @@ static at::Tensor swizzle_frag(const at::Tensor& W) {
       .view({-1});
 }
 
+// Rows per workgroup slab of the chain kernels (csrc/fwd_chain.hip,
+// csrc/bwd_chain.hip): 32 or 64. The bindings' ``rows`` argument picks
+// per call; 0 means the default, which is RSDL_CHAIN_ROWS if set (read
+// once) and the build's default otherwise. Only the grouping of the
+// loss/db partials depends on it; every per-row output is bit-identical.
+#ifndef RSDL_CHAIN_ROWS_DEFAULT
+#define RSDL_CHAIN_ROWS_DEFAULT 64
+#endif
+static int chain_rows(int64_t rows) {
+  if (rows == 0) {
+    static const int64_t latched = [] {
+      const char* e = std::getenv("RSDL_CHAIN_ROWS");
+      return (e != nullptr && *e != '\0')
+                 ? static_cast<int64_t>(std::atoll(e))
+                 : static_cast<int64_t>(RSDL_CHAIN_ROWS_DEFAULT);
+    }();
+    rows = latched;
+  }
+  TORCH_CHECK(rows == 32 || rows == 64,
+              "chain rows must be 32 or 64 (argument or RSDL_CHAIN_ROWS), "
+              "got ", rows);
+  return static_cast<int>(rows);
+}
+
 // Buffers + launches of the forward chain, shared by fwd_chain_bf16 and
 // fused_step_bf16. Weights arrive fragment-major (W1 with K padded to
 // 112), biases fp32, ``tgt`` fp32 [M] or nullptr. Nothing is launched for
@@ -664,7 +688,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
                           const at::Tensor& b2f, const at::Tensor& b3f,
                           const at::Tensor& b4f, const at::Tensor* tgt,
                           const c10::optional<at::Tensor>& xt_out,
-                          bool pi16) {
+                          bool pi16, int rows) {
   FwdChainOut f;
   const int64_t M = x.size(0);
   // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
@@ -684,7 +708,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
   float* lp_ptr = nullptr;
   if (tgt != nullptr) {
     f.dyb = at::empty({M, 1}, x.options());
-    f.loss_part = at::empty({std::max<int64_t>(fwd_chain_grid(M), 1)},
+    f.loss_part = at::empty({std::max<int64_t>(fwd_chain_grid(M, rows), 1)},
                             x.options().dtype(at::kFloat));
     tgt_ptr = tgt->data_ptr<float>();
     dyb_ptr = f.dyb.data_ptr();
@@ -716,7 +740,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
         f.a2t.data_ptr(),
         reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
         f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
-        pi16 ? 1 : 0, current_stream());
+        pi16 ? 1 : 0, rows, current_stream());
   }
   return f;
 }
@@ -726,7 +750,8 @@ std::vector<at::Tensor> fwd_chain_bf16(
     const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& W3,
     const at::Tensor& b3, const at::Tensor& w4, const at::Tensor& b4,
     const c10::optional<at::Tensor>& target,
-    const c10::optional<at::Tensor>& xt_out, bool pi16) {
+    const c10::optional<at::Tensor>& xt_out, bool pi16, int64_t rows) {
+  const int crows = chain_rows(rows);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fwd_chain: x must be contiguous bf16 [M,100]");
@@ -772,7 +797,7 @@ std::vector<at::Tensor> fwd_chain_bf16(
     W3s = swizzle_frag(W3);
   }
   auto f = run_fwd_chain(x, W1s, W2s, W3s, w4, b1f, b2f, b3f, b4f,
-                         with_loss ? &tgt : nullptr, xt_out, pi16);
+                         with_loss ? &tgt : nullptr, xt_out, pi16, crows);
   if (with_loss) {
     return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out, f.dyb,
             f.loss_part};
@@ -810,7 +835,7 @@ struct BwdChainOut {
 BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
                           const at::Tensor& mask1, const at::Tensor& mask2,
                           const at::Tensor& w4c, const at::Tensor& W3Ts,
-                          const at::Tensor& W2Ts, bool pi16) {
+                          const at::Tensor& W2Ts, bool pi16, int rows) {
   BwdChainOut b;
   const int64_t M = dy.size(0);
   const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
@@ -819,7 +844,7 @@ BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
   b.dz1t = at::empty({16 * mchunks * 512}, dy.options());
   b.dz2t = at::empty({8 * mchunks * 512}, dy.options());
   b.dz3t = at::empty({4 * mchunks * 512}, dy.options());
-  const int64_t grid = bwd_chain_grid(M);
+  const int64_t grid = bwd_chain_grid(M, rows);
   b.db_part = at::empty({std::max<int64_t>(grid, 1), kPartWPad},
                         dy.options().dtype(at::kFloat));
   if (M == 0) b.db_part.zero_();
@@ -828,7 +853,7 @@ BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
                      mask2.data_ptr(), w4c.data_ptr(), W3Ts.data_ptr(),
                      W2Ts.data_ptr(), b.dz1t.data_ptr(), b.dz2t.data_ptr(),
                      b.dz3t.data_ptr(), b.db_part.data_ptr<float>(), M,
-                     pi16 ? 1 : 0, current_stream());
+                     pi16 ? 1 : 0, rows, current_stream());
   }
   return b;
 }
@@ -836,7 +861,8 @@ BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
 std::vector<at::Tensor> bwd_chain_bf16(
     const at::Tensor& dy, const at::Tensor& a3, const at::Tensor& mask1,
     const at::Tensor& mask2, const at::Tensor& w4, const at::Tensor& W3,
-    const at::Tensor& W2, bool pi16) {
+    const at::Tensor& W2, bool pi16, int64_t rows) {
+  const int crows = chain_rows(rows);
   const int64_t M = dy.size(0);
   const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
@@ -875,7 +901,8 @@ std::vector<at::Tensor> bwd_chain_bf16(
                                   : swizzle_frag(W3.contiguous());
   auto W2Ts = (W2.size(0) == 256) ? swizzle_frag_T(W2.contiguous())
                                   : swizzle_frag(W2.contiguous());
-  auto bo = run_bwd_chain(dy, a3, mask1, mask2, w4c, W3Ts, W2Ts, pi16);
+  auto bo = run_bwd_chain(dy, a3, mask1, mask2, w4c, W3Ts, W2Ts, pi16,
+                          crows);
   auto& dz1t = bo.dz1t;
   auto& dz2t = bo.dz2t;
   auto& dz3t = bo.dz3t;
@@ -1150,7 +1177,8 @@ std::vector<at::Tensor> fused_step_bf16(
     const at::Tensor& x, const at::Tensor& target,
     const std::vector<at::Tensor>& weights,
     const std::vector<at::Tensor>& biases, bool pi16,
-    const c10::optional<std::vector<at::Tensor>>& outs) {
+    const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows) {
+  const int crows = chain_rows(rows);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fused_step: x must be contiguous bf16 [M,100]");
@@ -1171,9 +1199,10 @@ std::vector<at::Tensor> fused_step_bf16(
   c10::optional<at::Tensor> xt =
       at::empty({4 * mchunks * 512}, x.options());
   auto f = run_fwd_chain(x, pr.W1s, pr.W2s, pr.W3s, pr.w4b, biases[0],
-                         biases[1], biases[2], biases[3], &pr.tgt, xt, pi16);
+                         biases[1], biases[2], biases[3], &pr.tgt, xt, pi16,
+                         crows);
   auto b = run_bwd_chain(f.dyb, f.a3, f.mask1, f.mask2, pr.w4b, pr.W3Ts,
-                         pr.W2Ts, pi16);
+                         pr.W2Ts, pi16, crows);
   // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
   const char* st = std::getenv("RSDL_WGRAD_SMALL_TILES");
   const int64_t kt23 = (st != nullptr && std::strcmp(st, "1") == 0) ? 4 : 8;
@@ -1222,10 +1251,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("W1"), py::arg("b1"), py::arg("W2"), py::arg("b2"),
         py::arg("W3"), py::arg("b3"), py::arg("w4"), py::arg("b4"),
         py::arg("target") = c10::nullopt,
-        py::arg("xt_out") = c10::nullopt, py::arg("pi16") = false);
+        py::arg("xt_out") = c10::nullopt, py::arg("pi16") = false,
+        py::arg("rows") = 0);
   m.def("bwd_chain_bf16", &rsdl::bwd_chain_bf16, py::arg("dy"),
         py::arg("a3"), py::arg("mask1"), py::arg("mask2"), py::arg("w4"),
-        py::arg("W3"), py::arg("W2"), py::arg("pi16") = false);
+        py::arg("W3"), py::arg("W2"), py::arg("pi16") = false,
+        py::arg("rows") = 0);
   m.def("step_prep", &rsdl::step_prep, py::arg("weights"),
         py::arg("target") = c10::nullopt, py::arg("outs") = c10::nullopt);
   m.def("step_finalize", &rsdl::step_finalize, py::arg("part1"),
@@ -1233,7 +1264,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("loss_part"), py::arg("M"), py::arg("outs") = c10::nullopt);
   m.def("fused_step_bf16", &rsdl::fused_step_bf16, py::arg("x"),
         py::arg("target"), py::arg("weights"), py::arg("biases"),
-        py::arg("pi16") = false, py::arg("outs") = c10::nullopt);
+        py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
+        py::arg("rows") = 0);
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

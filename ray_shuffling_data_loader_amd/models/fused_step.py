@@ -42,6 +42,14 @@ from ray_shuffling_data_loader_amd.models.mlp import TabularMLP
 # override via fused_step._PI16.
 _PI16 = os.environ.get("RSDL_PI16", "0") == "1"
 
+# Rows per workgroup slab of the chain kernels (RSDL_CHAIN_ROWS=32|64):
+# a 64-row workgroup issues every weight fragment it loads against two
+# 32-row m-tiles, halving the weight traffic per row; only the grouping
+# of the loss/db partials differs between the two (csrc/fwd_chain.hip).
+# 0 = the extension's default (its own RSDL_CHAIN_ROWS latch, then the
+# build's default). Tests may override via fused_step._CHAIN_ROWS.
+_CHAIN_ROWS = int(os.environ.get("RSDL_CHAIN_ROWS", "0") or "0")
+
 # Native glue (default on; RSDL_NATIVE_GLUE=0 or fused_step._NATIVE_GLUE =
 # False forces the composed path): the whole schedule runs inside one
 # extension call, hip.fused_step_bf16, with the weight staging and the
@@ -86,6 +94,12 @@ def _weight_buffers(model: TabularMLP, lin):
         ],
     )
     return buf
+
+
+def _rows_kw() -> dict:
+    """``rows=`` for the chain bindings; empty at the default, which also
+    keeps the call valid for stand-ins that predate the argument."""
+    return {"rows": _CHAIN_ROWS} if _CHAIN_ROWS else {}
 
 
 def _native_ok(hip, lin, x, target, grad_hook) -> bool:
@@ -151,7 +165,7 @@ def fused_step(
                 x, target,
                 [m.weight.detach() for m in lin],
                 [m.bias.detach() for m in lin],
-                pi16=_PI16, outs=outs,
+                pi16=_PI16, outs=outs, **_rows_kw(),
             )
             if outs is None:
                 # dW1..dW4 then db1..db4, fresh fp32 tensors in the
@@ -172,13 +186,14 @@ def fused_step(
                      device=x.device)
     a1t, mask1, a2t, mask2, a3, out, dyb, loss_part = hip.fwd_chain_bf16(
         x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"], b4,
-        target=target, xt_out=xt, pi16=_PI16,
+        target=target, xt_out=xt, pi16=_PI16, **_rows_kw(),
     )
     loss = loss_part.sum() / M
     # Backward chain: consumes the masks (never the activations), emits
     # dz^T fragments; dW4/db4 partials fold into its seed loop.
     dz1t, dz2t, dz3t, db1, db2, db3, db4, dw4 = hip.bwd_chain_bf16(
-        dyb, a3, mask1, mask2, buf["w4"], buf["W3"], buf["W2"], pi16=_PI16
+        dyb, a3, mask1, mask2, buf["w4"], buf["W3"], buf["W2"], pi16=_PI16,
+        **_rows_kw(),
     )
     # The DP bench pre-creates .grad as views of one flat buffer (so the
     # gradient all-reduce is a single collective) and marks the model;
