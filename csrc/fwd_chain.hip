@@ -58,7 +58,8 @@
 // Validated by tests/test_gpu_kernels.py (chain numerics, layout
 // oracles, whole-step parity), tests/test_chain_rows64_gpu.py (64-row
 // slabs bit-equal to 32-row ones, odd tile counts, regrouped partials)
-// and tests/test_chain_sim.py (lane-level index simulation).
+// and tests/test_chain_sim.py (lane-level index simulation); the
+// forward-only eval_chain_kernel by tests/test_fused_eval_gpu.py.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -481,6 +482,113 @@ fwd_chain_kernel(
   fc_store_tile<MT, FC_N3, FC_S3>(t3, a3, m0, M, tid);
 }
 
+// Forward-only sibling of fwd_chain_kernel for evaluation
+// (models/fused_eval.py): the same slab scheme, LDS aliasing, barriers and
+// three fc_layer calls, with EMIT_T off in layers 1 and 2 — no transposed
+// fragments, no mask words, no a3 tile and no dyb leave the workgroup.
+// Every accumulator sees the MFMAs of the training kernel in the same
+// order, so the head value o is the training kernel's, bit for bit.
+//   pred (optional)    pred[m] = o, fp32, unrounded
+//   target (optional)  part[blockIdx][0..3] = sum (o-t)^2, sum |o-t|,
+//                      sum t, sum t^2 over the slab's rows m < M.
+// Column 0 is loss_part of the training kernel: the same diff and d2
+// expressions and the same serial sum over lsum[0..ROWS) by one thread.
+// Columns 1-3 are summed the same way by threads 1-3. A separate kernel,
+// not a template flag of fwd_chain_kernel: the 64-row training
+// instantiation sits at exactly 128 registers and must not move.
+template <int MT>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+eval_chain_kernel(
+    const short* __restrict__ x0s,  // fragment-major swizzled x
+    const short* __restrict__ W1, const float* __restrict__ b1,
+    const short* __restrict__ W2, const float* __restrict__ b2,
+    const short* __restrict__ W3, const float* __restrict__ b3,
+    const short* __restrict__ w4, const float* __restrict__ b4,
+    float* __restrict__ pred, const float* __restrict__ target,
+    float* __restrict__ part, int64_t M, int64_t mchunks) {
+  // LDS plan of fwd_chain_kernel, with four lsum columns instead of one
+  // (MT = 1: 50.7 KB, 3 workgroups/CU; MT = 2: 67.6 KB, 2 workgroups/CU).
+  constexpr int ROWS = MT * FC_MT;
+  constexpr int T1B = ROWS * FC_S1 * 2;
+  constexpr int T2B = ROWS * FC_S2 * 2;
+  constexpr int TILEB = MT == 1 ? T1B + T2B : T1B;
+  static_assert(MT == 1 || T2B + ROWS * FC_S3 * 2 <= T1B, "t2+t3 in t1");
+  __shared__ __align__(16) char smem[TILEB + 4 * ROWS * 4];
+  short* t1 = reinterpret_cast<short*>(smem);
+  short* t2 = reinterpret_cast<short*>(MT == 1 ? smem + T1B : smem);
+  // aliased: live ranges are disjoint (barrier-ordered)
+  short* t3 = reinterpret_cast<short*>(MT == 1 ? smem : smem + T2B);
+  float* lsum = reinterpret_cast<float*>(smem + TILEB);  // [4][ROWS]
+
+  const int64_t m0 = (int64_t)blockIdx.x * ROWS;
+  const int32_t tid = threadIdx.x;
+  const int32_t wave = tid >> 6;
+  const int32_t lane = tid & 63;
+  const int64_t mt_g0 = (int64_t)blockIdx.x * MT;  // first global m-tile
+  // Workgroup-uniform: the slab's second m-tile exists (see fc_layer).
+  const bool has2 = MT == 1 || 2 * (mt_g0 + 1) < mchunks;
+
+  const short* xblk = &x0s[mt_g0 * (FC_K0P / 16) * 512];
+  constexpr int NT1 = FC_N1 / (128 * MT), NT2 = FC_N2 / (128 * MT);
+  fc_layer<FC_K0P, FC_N1, MT, NT1, 0, FC_S1, true, true>(
+      xblk, W1, b1, t1, 0, wave * NT1, fc_fresh_lane<MT>(lane), has2);
+  __syncthreads();
+  fc_layer<FC_N1, FC_N2, MT, NT2, FC_S1, FC_S2, true, false, false, false,
+           MT == 2>(
+      t1, W2, b2, t2, 0, wave * NT2, fc_fresh_lane<MT>(lane), has2);
+  __syncthreads();
+  fc_layer<FC_N2, FC_N3, 1, 1, FC_S2, FC_S3, true>(
+      t2, W3, b3, t3, wave >> 2, wave & 3, fc_fresh_lane<MT>(lane), true);
+  __syncthreads();
+
+  // Head as in fwd_chain_kernel: 8 threads per row, shuffle reduce.
+  {
+    constexpr int TPR = 256 / FC_MT;       // threads per row
+    constexpr int KPT = FC_N3 / TPR;       // k per thread
+    const int32_t m = tid / TPR;
+    const int32_t prt = tid % TPR;
+    float s = 0.f;
+    #pragma unroll
+    for (int32_t kk = 0; kk < KPT; kk++) {
+      const int32_t k = prt * KPT + kk;
+      s += fc_b2f(t3[m * FC_S3 + k]) * fc_b2f(w4[k]);
+    }
+    #pragma unroll
+    for (int32_t d = 1; d < TPR; d <<= 1) {
+      s += __shfl_down(s, d);
+    }
+    if (prt == 0) {
+      const float o = s + b4[0];
+      float d2 = 0.f, ad = 0.f, t = 0.f;
+      if (m0 + m < M) {
+        if (pred != nullptr) pred[m0 + m] = o;
+        if (target != nullptr) {
+          t = target[m0 + m];
+          const float diff = o - t;
+          d2 = diff * diff;
+          ad = fabsf(diff);
+        }
+      }
+      if (target != nullptr) {
+        lsum[m] = d2;
+        lsum[ROWS + m] = ad;
+        lsum[2 * ROWS + m] = t;
+        lsum[3 * ROWS + m] = t * t;
+      }
+    }
+  }
+  if (target != nullptr) {
+    __syncthreads();
+    if (tid < 4) {
+      const float* col = lsum + tid * ROWS;
+      float s = 0.f;
+      #pragma unroll
+      for (int32_t m = 0; m < ROWS; m++) s += col[m];
+      part[(int64_t)blockIdx.x * 4 + tid] = s;
+    }
+  }
+}
+
 // x [M,100] bf16 -> fragment-major [ceil(M/32)][7][2][32][8] with zero
 // padding (cols 100..111 and rows past M). One thread per 8-halfword
 // fragment slice; replaces a 3-kernel pad+permute+contiguous chain.
@@ -693,6 +801,26 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                      reinterpret_cast<short*>(out), target,
                      reinterpret_cast<short*>(dyb), loss_part,
                      target ? 1.f / (float)M : 0.f, M, mchunks);
+}
+
+// Forward-only evaluation chain: ``pred`` (fp32 [M]) and/or ``target``
+// with ``part`` (fp32 [fwd_chain_grid(M, rows), 4]); either may be null.
+void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
+                       const void* W2, const float* b2, const void* W3,
+                       const float* b3, const void* w4, const float* b4,
+                       float* pred, const float* target, float* part,
+                       int64_t M, int rows, hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
+  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
+  auto kern = rows == 64 ? eval_chain_kernel<2> : eval_chain_kernel<1>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+                     stream,
+                     reinterpret_cast<const short*>(x0s),
+                     reinterpret_cast<const short*>(W1), b1,
+                     reinterpret_cast<const short*>(W2), b2,
+                     reinterpret_cast<const short*>(W3), b3,
+                     reinterpret_cast<const short*>(w4), b4, pred, target,
+                     part, M, mchunks);
 }
 
 }  // namespace rsdl

@@ -13,6 +13,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <tuple>
 #include <vector>
 
 #include "step_glue.h"
@@ -113,6 +114,11 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       uint32_t* mask2, void* a3, void* out,
                       const float* target, void* dyb, float* loss_part,
                       int64_t M, int pi16, int rows, hipStream_t stream);
+void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
+                       const void* W2, const float* b2, const void* W3,
+                       const float* b3, const void* w4, const float* b4,
+                       float* pred, const float* target, float* part,
+                       int64_t M, int rows, hipStream_t stream);
 int64_t bwd_chain_grid(int64_t M, int rows);
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
@@ -1212,6 +1218,123 @@ std::vector<at::Tensor> fused_step_bf16(
   return run_step_finalize(p1, p2, p3, b.db_part, f.loss_part, M, outs);
 }
 
+// Forward-only evaluation of the stock TabularMLP (csrc/fwd_chain.hip,
+// eval_chain_kernel): x swizzle + one chain launch that writes fp32
+// predictions and/or four metric partials per workgroup, and none of the
+// training by-products. ``Wstage`` = [W1s, W2s, W3s, w4b], the bf16
+// fragment-major buffers step_prep produces (staged once by the caller,
+// not per call); ``biases`` fp32, read directly. ``target`` fp32 or fp64
+// (cast to fp32 first) with M elements -> part fp32 [grid, 4] =
+// {sum (o-t)^2, sum |o-t|, sum t, sum t^2} per slab of ``rows`` rows;
+// column 0 is bit-identical to fwd_chain_bf16's loss_part. ``pred_out``:
+// caller-owned contiguous fp32 with M elements (may be a view into a
+// larger buffer). Returns (pred or None, part or None). No sync, no host
+// read: graph-capture safe.
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>>
+eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
+                const std::vector<at::Tensor>& biases,
+                const c10::optional<at::Tensor>& target,
+                const c10::optional<at::Tensor>& pred_out, bool want_pred,
+                int64_t rows) {
+  const int crows = chain_rows(rows);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
+              "eval_chain: x must be contiguous bf16 [M,100]");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(Wstage.size() == 4,
+              "eval_chain: Wstage must be [W1s, W2s, W3s, w4b]");
+  const int64_t wn[4] = {512 * 112, 256 * 512, 128 * 256, 128};
+  for (int i = 0; i < 4; i++) {
+    TORCH_CHECK(Wstage[i].is_cuda() &&
+                    Wstage[i].scalar_type() == at::kBFloat16 &&
+                    Wstage[i].is_contiguous() && Wstage[i].numel() == wn[i] &&
+                    Wstage[i].get_device() == x.get_device() &&
+                    reinterpret_cast<uintptr_t>(Wstage[i].data_ptr()) % 16 ==
+                        0,
+                "eval_chain: staged weight ", i,
+                " must be contiguous aligned bf16 with ", wn[i],
+                " elements on x's GPU");
+  }
+  TORCH_CHECK(biases.size() == 4, "eval_chain: biases must be [b1..b4]");
+  const int64_t bn[4] = {512, 256, 128, 1};
+  for (int i = 0; i < 4; i++) {
+    TORCH_CHECK(biases[i].is_cuda() &&
+                    biases[i].scalar_type() == at::kFloat &&
+                    biases[i].is_contiguous() && biases[i].numel() == bn[i] &&
+                    biases[i].get_device() == x.get_device(),
+                "eval_chain: bias ", i, " must be contiguous fp32 [", bn[i],
+                "] on x's GPU");
+  }
+  const bool with_pred = want_pred || pred_out.has_value();
+  TORCH_CHECK(with_pred || target.has_value(),
+              "eval_chain: nothing to compute (no target, no predictions)");
+  at::Tensor tgt, pred, part;
+  if (target.has_value()) {
+    TORCH_CHECK(target->is_cuda() &&
+                    target->get_device() == x.get_device() &&
+                    (target->scalar_type() == at::kFloat ||
+                     target->scalar_type() == at::kDouble),
+                "eval_chain: target must be fp32 or fp64 on x's GPU");
+    TORCH_CHECK(target->numel() == M, "eval_chain: target size mismatch");
+    tgt = target->reshape({-1}).to(at::kFloat).contiguous();
+  }
+  if (pred_out.has_value()) {
+    TORCH_CHECK(pred_out->is_cuda() &&
+                    pred_out->get_device() == x.get_device() &&
+                    pred_out->scalar_type() == at::kFloat &&
+                    pred_out->is_contiguous() && pred_out->numel() == M,
+                "eval_chain: pred_out must be contiguous fp32 with ", M,
+                " elements on x's GPU");
+    pred = *pred_out;
+  } else if (with_pred) {
+    pred = at::empty({M}, x.options().dtype(at::kFloat));
+  }
+  const int64_t grid = M > 0 ? fwd_chain_grid(M, crows) : 0;
+  if (target.has_value()) {
+    part = M > 0 ? at::empty({grid, 4}, x.options().dtype(at::kFloat))
+                 : at::zeros({1, 4}, x.options().dtype(at::kFloat));
+  }
+  if (M > 0) {
+    const int64_t Mp = (M + 31) / 32 * 32;
+    auto xs = at::empty({Mp * 112}, x.options());
+    launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
+    launch_eval_chain(
+        xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
+        Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
+        Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
+        Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
+        with_pred ? pred.data_ptr<float>() : nullptr,
+        target.has_value() ? tgt.data_ptr<float>() : nullptr,
+        target.has_value() ? part.data_ptr<float>() : nullptr, M, crows,
+        current_stream());
+  }
+  c10::optional<at::Tensor> po, pa;
+  if (with_pred) po = pred;
+  if (target.has_value()) pa = part;
+  return {po, pa};
+}
+
+// acc[5] = {rows, sse, sae, sum_t, sum_tt} (fp64, persistent) += M and
+// the column sums of ``part`` [n, 4], in place, one launch, fixed order
+// (csrc/step_glue.hip).
+void eval_accumulate(const at::Tensor& part, const at::Tensor& acc,
+                     int64_t M) {
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat &&
+                  part.is_contiguous() && part.dim() == 2 &&
+                  part.size(1) == 4 &&
+                  reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+              "eval_accumulate: part must be contiguous aligned fp32 [n,4] "
+              "on GPU");
+  TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kDouble &&
+                  acc.is_contiguous() && acc.numel() == 5 &&
+                  acc.get_device() == part.get_device(),
+              "eval_accumulate: acc must be contiguous fp64 [5] on part's "
+              "GPU");
+  TORCH_CHECK(M >= 0, "eval_accumulate: M must not be negative");
+  launch_eval_accumulate(part.data_ptr<float>(), part.size(0), M,
+                         acc.data_ptr<double>(), current_stream());
+}
+
 }  // namespace rsdl
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1266,6 +1389,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("target"), py::arg("weights"), py::arg("biases"),
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
         py::arg("rows") = 0);
+  m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
+        py::arg("Wstage"), py::arg("biases"),
+        py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,
+        py::arg("want_pred") = true, py::arg("rows") = 0);
+  m.def("eval_accumulate", &rsdl::eval_accumulate, py::arg("part"),
+        py::arg("acc"), py::arg("M"));
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

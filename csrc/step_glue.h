@@ -43,5 +43,8 @@ struct StepFinArgs {
 
 void launch_step_prep(const StepPrepArgs& p, hipStream_t stream);
 void launch_step_finalize(const StepFinArgs& p, hipStream_t stream);
+// part fp32 [nrows, 4] (16-byte aligned) -> acc fp64 [5] += {M, column sums}
+void launch_eval_accumulate(const float* part, int64_t nrows, int64_t M,
+                            double* acc, hipStream_t stream);
 
 }  // namespace rsdl

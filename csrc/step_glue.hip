@@ -12,6 +12,8 @@
 //                  and the scalar loss. Writes every output element
 //                  exactly once (no zero-fill, no atomics) and sums in a
 //                  fixed order, so equal partials give bit-equal results.
+//   eval_accumulate  the evaluation chain's per-workgroup metric partials
+//                  -> a persistent fp64 accumulator (models/fused_eval.py).
 //
 // Fragment-major layout (see csrc/fwd_chain.hip): a [N,K] matrix becomes
 // [N/32][K/16][2][32][8]; element (a,c,h,r,e) is W[a*32+r][c*16+h*8+e].
@@ -347,6 +349,54 @@ __global__ void __launch_bounds__(256) step_finalize_kernel(StepFinArgs p) {
 void launch_step_finalize(const StepFinArgs& p, hipStream_t stream) {
   hipLaunchKernelGGL(step_finalize_kernel, dim3(SG_FIN_BLOCKS), dim3(256), 0,
                      stream, p);
+}
+
+// ---------------------------------------------------------------------
+// eval_accumulate
+//
+// Folds the evaluation chain's per-workgroup partials part[nrows][4] =
+// {sum (o-t)^2, sum |o-t|, sum t, sum t^2} (fp32, csrc/fwd_chain.hip) into
+// the persistent fp64 accumulator acc[5] = {rows, sse, sae, sum_t, sum_tt},
+// in place. One workgroup: thread i sums partial rows i, i + 256, ... in
+// fp64, the 256 shares meet in a fixed LDS tree, and thread 0 adds the
+// totals and M into acc. No atomics, no zero fill, no host read: the same
+// partials in the same order give the same bits, and the launch can be
+// captured in a graph.
+// ---------------------------------------------------------------------
+__global__ void __launch_bounds__(256) eval_accumulate_kernel(
+    const float* __restrict__ part, int64_t nrows, int64_t M,
+    double* __restrict__ acc) {
+  __shared__ double lds[4][256];
+  const int32_t tid = threadIdx.x;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  // unrolled so several loads are in flight; the add order is unchanged
+  #pragma unroll 4
+  for (int64_t r = tid; r < nrows; r += 256) {
+    const sg_f32x4 v = reinterpret_cast<const sg_f32x4*>(part)[r];
+    #pragma unroll
+    for (int e = 0; e < 4; e++) a[e] += (double)v[e];
+  }
+  #pragma unroll
+  for (int e = 0; e < 4; e++) lds[e][tid] = a[e];
+  __syncthreads();
+  for (int32_t d = 128; d > 0; d >>= 1) {
+    if (tid < d) {
+      #pragma unroll
+      for (int e = 0; e < 4; e++) lds[e][tid] += lds[e][tid + d];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    acc[0] += (double)M;
+    #pragma unroll
+    for (int e = 0; e < 4; e++) acc[1 + e] += lds[e][0];
+  }
+}
+
+void launch_eval_accumulate(const float* part, int64_t nrows, int64_t M,
+                            double* acc, hipStream_t stream) {
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(256), 0, stream,
+                     part, nrows, M, acc);
 }
 
 }  // namespace rsdl
