@@ -59,7 +59,9 @@
 // oracles, whole-step parity), tests/test_chain_rows64_gpu.py (64-row
 // slabs bit-equal to 32-row ones, odd tile counts, regrouped partials)
 // and tests/test_chain_sim.py (lane-level index simulation); the
-// forward-only eval_chain_kernel by tests/test_fused_eval_gpu.py.
+// forward-only eval_chain_kernel by tests/test_fused_eval_gpu.py; the BCE
+// head, the binary task and the AUC histogram by
+// tests/test_fused_bce_gpu.py.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -164,10 +166,15 @@ __device__ __forceinline__ short fc_f2b(float f) {
 // one uniform flag — no per-element guards in the loops.
 // SYNC_EPI: a workgroup barrier between the k-loop and the epilogue, for
 // a dst tile that aliases the src tile.
+// __forceinline__: the chain kernels are instantiated once per loss /
+// task, so each emitting layer has more than one caller; left to its cost
+// model the compiler then keeps the layers out-of-line, and the 64-row
+// training kernel spills (200 B of scratch) at its 128-register cap.
+// Inlined, every instantiation has the single-caller figures.
 template <int K, int N, int MPW, int NT, int SRC_S, int DST_S, bool RELU,
           bool A_FRAGMAJOR = false, bool EMIT_T = false, bool PI16 = false,
           bool SYNC_EPI = false>
-__device__ void fc_layer(
+__device__ __forceinline__ void fc_layer(
     const short* __restrict__ src_lds, const short* __restrict__ W,
     const float* __restrict__ bias, short* __restrict__ dst_lds,
     int32_t mt0, int32_t ntile0, int32_t lane, bool has2,
@@ -352,6 +359,24 @@ __device__ void fc_store_tile(const short* __restrict__ lds, short* out,
   }
 }
 
+// Logistic head shared by the BCE instantiations of both chain kernels:
+// for the fp32 logit o, e = exp(-|o|) never overflows, the sigmoid is
+// 1/(1+e) or e/(1+e) by the sign of o, and the per-row loss is the
+// softplus form max(o,0) - o*t + log1p(e), finite at any finite o (the
+// naive log(1+exp(o)) is inf from o ~ 89). expf/log1pf, not the fast
+// intrinsics: the test tolerances are derived from them.
+__device__ __forceinline__ void fc_bce_terms(float o, float t, float& sg,
+                                             float& l) {
+  const float e = expf(-fabsf(o));
+  sg = o >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+  l = fmaxf(o, 0.f) - o * t + log1pf(e);
+}
+
+// Loss selector of fwd_chain_kernel / task selector of eval_chain_kernel
+// (exported by the binding as LOSS_MSE / LOSS_BCE).
+#define FC_LOSS_MSE 0
+#define FC_LOSS_BCE 1
+
 // The 64-row kernels run at exactly 128 registers. Handing each layer an
 // opaque copy of the lane index keeps the compiler from carrying lane-
 // derived address terms across a whole layer (it spilled one to scratch
@@ -366,7 +391,10 @@ __device__ __forceinline__ int32_t fc_fresh_lane(int32_t lane) {
 // the header for the slab-size reasoning. The second __launch_bounds__
 // figure is waves per SIMD: the 64-row kernel must fit 128 registers so
 // that two 8-wave workgroups share a CU.
-template <int MT, bool PI16>
+// LOSS picks the head epilogue only (FC_LOSS_MSE: dyb = 2/M (o-t), terms
+// (o-t)^2; FC_LOSS_BCE: dyb = 1/M (sigmoid(o)-t), terms from
+// fc_bce_terms); the layers, the LDS plan and the barriers do not see it.
+template <int MT, bool PI16, int LOSS = FC_LOSS_MSE>
 __global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
 fwd_chain_kernel(
     const short* __restrict__ x0s,  // fragment-major swizzled x (see note)
@@ -379,10 +407,10 @@ fwd_chain_kernel(
     short* __restrict__ a2t,        // wgrad fragment-major a2^T
     uint32_t* __restrict__ mask2,   // [m_tiles][256]
     short* __restrict__ a3, short* __restrict__ out,
-    // Optional fused MSE epilogue (target != nullptr): dyb[m] =
+    // Optional fused loss epilogue (target != nullptr), MSE: dyb[m] =
     // (2/M)*(out[m]-target[m]) in bf16 and loss_part[blockIdx] =
     // sum_m (out[m]-target[m])^2 — removes the eager loss/grad kernel
-    // chain from the fused train step.
+    // chain from the fused train step. BCE: see LOSS above.
     const float* __restrict__ target, short* __restrict__ dyb,
     float* __restrict__ loss_part, float inv_m, int64_t M,
     int64_t mchunks) {
@@ -461,9 +489,16 @@ fwd_chain_kernel(
       if (m0 + m < M) {
         out[m0 + m] = fc_f2b(o);
         if (target != nullptr) {
-          const float diff = o - target[m0 + m];
-          dyb[m0 + m] = fc_f2b(2.f * inv_m * diff);
-          d2 = diff * diff;
+          if (LOSS == FC_LOSS_MSE) {
+            const float diff = o - target[m0 + m];
+            dyb[m0 + m] = fc_f2b(2.f * inv_m * diff);
+            d2 = diff * diff;
+          } else {
+            float sg;
+            const float t = target[m0 + m];
+            fc_bce_terms(o, t, sg, d2);
+            dyb[m0 + m] = fc_f2b(inv_m * (sg - t));
+          }
         }
       }
       if (target != nullptr) lsum[m] = d2;
@@ -496,7 +531,17 @@ fwd_chain_kernel(
 // Columns 1-3 are summed the same way by threads 1-3. A separate kernel,
 // not a template flag of fwd_chain_kernel: the 64-row training
 // instantiation sits at exactly 128 registers and must not move.
-template <int MT>
+// TASK = FC_LOSS_BCE (binary classification, o is a logit): the partials
+// are {sum l, sum (sg-t)^2, sum t, sum correct} with l and sg from
+// fc_bce_terms as in the training kernel and correct = ((o >= 0) ==
+// (t >= 0.5)) — at most ROWS per slab, exact in fp32. With ``hist``
+// (int64 [2][65536], persistent, optional) every row m < M also adds 1
+// to hist[t >= 0.5][key], key = the top 16 bits of the order-preserving
+// transform of o's bit pattern (o truncated to bf16 precision, order
+// kept): the streaming-AUC histogram. Integer atomics commute, so the
+// histogram does not depend on launch or arrival order. A NaN logit lands
+// wherever its bits put it. ``hist`` is ignored by the regression task.
+template <int MT, int TASK = FC_LOSS_MSE>
 __global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
 eval_chain_kernel(
     const short* __restrict__ x0s,  // fragment-major swizzled x
@@ -505,7 +550,8 @@ eval_chain_kernel(
     const short* __restrict__ W3, const float* __restrict__ b3,
     const short* __restrict__ w4, const float* __restrict__ b4,
     float* __restrict__ pred, const float* __restrict__ target,
-    float* __restrict__ part, int64_t M, int64_t mchunks) {
+    float* __restrict__ part, int64_t M, int64_t mchunks,
+    unsigned long long* __restrict__ hist) {
   // LDS plan of fwd_chain_kernel, with four lsum columns instead of one
   // (MT = 1: 50.7 KB, 3 workgroups/CU; MT = 2: 67.6 KB, 2 workgroups/CU).
   constexpr int ROWS = MT * FC_MT;
@@ -559,21 +605,36 @@ eval_chain_kernel(
     }
     if (prt == 0) {
       const float o = s + b4[0];
-      float d2 = 0.f, ad = 0.f, t = 0.f;
+      float d2 = 0.f, ad = 0.f, t = 0.f, c3 = 0.f;
       if (m0 + m < M) {
         if (pred != nullptr) pred[m0 + m] = o;
         if (target != nullptr) {
           t = target[m0 + m];
-          const float diff = o - t;
-          d2 = diff * diff;
-          ad = fabsf(diff);
+          if (TASK == FC_LOSS_MSE) {
+            const float diff = o - t;
+            d2 = diff * diff;
+            ad = fabsf(diff);
+          } else {
+            float sg;
+            fc_bce_terms(o, t, sg, d2);
+            const float diff = sg - t;
+            ad = diff * diff;
+            const bool cls = t >= 0.5f;
+            c3 = ((o >= 0.f) == cls) ? 1.f : 0.f;
+            if (hist != nullptr) {
+              const uint32_t bits = __float_as_uint(o);
+              const uint32_t u =
+                  bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+              atomicAdd(&hist[(cls ? 65536u : 0u) + (u >> 16)], 1ULL);
+            }
+          }
         }
       }
       if (target != nullptr) {
         lsum[m] = d2;
         lsum[ROWS + m] = ad;
         lsum[2 * ROWS + m] = t;
-        lsum[3 * ROWS + m] = t * t;
+        lsum[3 * ROWS + m] = TASK == FC_LOSS_MSE ? t * t : c3;
       }
     }
   }
@@ -781,13 +842,21 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       void* a1t, uint32_t* mask1, void* a2t,
                       uint32_t* mask2, void* a3, void* out,
                       const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, int rows, hipStream_t stream) {
+                      int64_t M, int pi16, int rows, int loss,
+                      hipStream_t stream) {
   const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
   // The global layouts are per 32-row m-tile whatever the slab size.
   const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
   auto kern = rows == 64
       ? (pi16 ? fwd_chain_kernel<2, true> : fwd_chain_kernel<2, false>)
       : (pi16 ? fwd_chain_kernel<1, true> : fwd_chain_kernel<1, false>);
+  if (loss == FC_LOSS_BCE) {
+    kern = rows == 64
+        ? (pi16 ? fwd_chain_kernel<2, true, FC_LOSS_BCE>
+                : fwd_chain_kernel<2, false, FC_LOSS_BCE>)
+        : (pi16 ? fwd_chain_kernel<1, true, FC_LOSS_BCE>
+                : fwd_chain_kernel<1, false, FC_LOSS_BCE>);
+  }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
                      stream,
                      reinterpret_cast<const short*>(x0s),
@@ -805,14 +874,21 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
 
 // Forward-only evaluation chain: ``pred`` (fp32 [M]) and/or ``target``
 // with ``part`` (fp32 [fwd_chain_grid(M, rows), 4]); either may be null.
+// ``task`` = FC_LOSS_MSE (regression partials) or FC_LOSS_BCE (binary
+// partials, plus the AUC histogram when ``hist`` is not null).
 void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
                        const void* W2, const float* b2, const void* W3,
                        const float* b3, const void* w4, const float* b4,
                        float* pred, const float* target, float* part,
-                       int64_t M, int rows, hipStream_t stream) {
+                       int64_t M, int rows, int task, int64_t* hist,
+                       hipStream_t stream) {
   const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
   const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
   auto kern = rows == 64 ? eval_chain_kernel<2> : eval_chain_kernel<1>;
+  if (task == FC_LOSS_BCE) {
+    kern = rows == 64 ? eval_chain_kernel<2, FC_LOSS_BCE>
+                      : eval_chain_kernel<1, FC_LOSS_BCE>;
+  }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
                      stream,
                      reinterpret_cast<const short*>(x0s),
@@ -820,7 +896,8 @@ void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
                      reinterpret_cast<const short*>(W2), b2,
                      reinterpret_cast<const short*>(W3), b3,
                      reinterpret_cast<const short*>(w4), b4, pred, target,
-                     part, M, mchunks);
+                     part, M, mchunks,
+                     reinterpret_cast<unsigned long long*>(hist));
 }
 
 }  // namespace rsdl

@@ -113,12 +113,14 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                       void* a1t, uint32_t* mask1, void* a2t,
                       uint32_t* mask2, void* a3, void* out,
                       const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, int rows, hipStream_t stream);
+                      int64_t M, int pi16, int rows, int loss,
+                      hipStream_t stream);
 void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
                        const void* W2, const float* b2, const void* W3,
                        const float* b3, const void* w4, const float* b4,
                        float* pred, const float* target, float* part,
-                       int64_t M, int rows, hipStream_t stream);
+                       int64_t M, int rows, int task, int64_t* hist,
+                       hipStream_t stream);
 int64_t bwd_chain_grid(int64_t M, int rows);
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
@@ -680,6 +682,18 @@ static int chain_rows(int64_t rows) {
   return static_cast<int>(rows);
 }
 
+// Objective of the fused head epilogue (csrc/fwd_chain.hip): the ``loss``
+// argument of fwd_chain_bf16 / fused_step_bf16 and the ``task`` argument
+// of eval_chain_bf16. Exported as LOSS_MSE / LOSS_BCE.
+constexpr int64_t kLossMse = 0;
+constexpr int64_t kLossBce = 1;
+static int chain_loss(int64_t loss, const char* who, const char* what) {
+  TORCH_CHECK(loss == kLossMse || loss == kLossBce, who, ": ", what,
+              " must be 0 (MSE / regression) or 1 (BCE / binary), got ",
+              loss);
+  return static_cast<int>(loss);
+}
+
 // Buffers + launches of the forward chain, shared by fwd_chain_bf16 and
 // fused_step_bf16. Weights arrive fragment-major (W1 with K padded to
 // 112), biases fp32, ``tgt`` fp32 [M] or nullptr. Nothing is launched for
@@ -694,7 +708,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
                           const at::Tensor& b2f, const at::Tensor& b3f,
                           const at::Tensor& b4f, const at::Tensor* tgt,
                           const c10::optional<at::Tensor>& xt_out,
-                          bool pi16, int rows) {
+                          bool pi16, int rows, int loss) {
   FwdChainOut f;
   const int64_t M = x.size(0);
   // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
@@ -746,7 +760,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
         f.a2t.data_ptr(),
         reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
         f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
-        pi16 ? 1 : 0, rows, current_stream());
+        pi16 ? 1 : 0, rows, loss, current_stream());
   }
   return f;
 }
@@ -756,8 +770,10 @@ std::vector<at::Tensor> fwd_chain_bf16(
     const at::Tensor& W2, const at::Tensor& b2, const at::Tensor& W3,
     const at::Tensor& b3, const at::Tensor& w4, const at::Tensor& b4,
     const c10::optional<at::Tensor>& target,
-    const c10::optional<at::Tensor>& xt_out, bool pi16, int64_t rows) {
+    const c10::optional<at::Tensor>& xt_out, bool pi16, int64_t rows,
+    int64_t loss) {
   const int crows = chain_rows(rows);
+  const int closs = chain_loss(loss, "fwd_chain", "loss");
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fwd_chain: x must be contiguous bf16 [M,100]");
@@ -787,9 +803,11 @@ std::vector<at::Tensor> fwd_chain_bf16(
   const int64_t M = x.size(0);
   // The kernel's A-fragment loads need W1's k-dim padded 100 -> 112.
   auto W1p = w1_padded ? W1 : at::constant_pad_nd(W1, {0, 12}).contiguous();
-  // Fused MSE epilogue: with a target, the kernel also emits the bf16
-  // loss gradient dyb = (2/M)(out - target) and per-block squared-error
-  // partials (loss = loss_part.sum()/M) — no eager loss/grad kernels.
+  // Fused loss epilogue: with a target, the kernel also emits the bf16
+  // loss gradient dyb and per-block loss partials (loss =
+  // loss_part.sum()/M) — no eager loss/grad kernels. LOSS_MSE: dyb =
+  // (2/M)(out - target), squared errors; LOSS_BCE: dyb = (1/M)
+  // (sigmoid(out) - target), logistic losses (out is the logit).
   const bool with_loss = target.has_value();
   at::Tensor tgt;
   if (with_loss) {
@@ -803,7 +821,8 @@ std::vector<at::Tensor> fwd_chain_bf16(
     W3s = swizzle_frag(W3);
   }
   auto f = run_fwd_chain(x, W1s, W2s, W3s, w4, b1f, b2f, b3f, b4f,
-                         with_loss ? &tgt : nullptr, xt_out, pi16, crows);
+                         with_loss ? &tgt : nullptr, xt_out, pi16, crows,
+                         closs);
   if (with_loss) {
     return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out, f.dyb,
             f.loss_part};
@@ -1183,8 +1202,10 @@ std::vector<at::Tensor> fused_step_bf16(
     const at::Tensor& x, const at::Tensor& target,
     const std::vector<at::Tensor>& weights,
     const std::vector<at::Tensor>& biases, bool pi16,
-    const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows) {
+    const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
+    int64_t loss) {
   const int crows = chain_rows(rows);
+  const int closs = chain_loss(loss, "fused_step", "loss");
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fused_step: x must be contiguous bf16 [M,100]");
@@ -1206,7 +1227,7 @@ std::vector<at::Tensor> fused_step_bf16(
       at::empty({4 * mchunks * 512}, x.options());
   auto f = run_fwd_chain(x, pr.W1s, pr.W2s, pr.W3s, pr.w4b, biases[0],
                          biases[1], biases[2], biases[3], &pr.tgt, xt, pi16,
-                         crows);
+                         crows, closs);
   auto b = run_bwd_chain(f.dyb, f.a3, f.mask1, f.mask2, pr.w4b, pr.W3Ts,
                          pr.W2Ts, pi16, crows);
   // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
@@ -1228,15 +1249,23 @@ std::vector<at::Tensor> fused_step_bf16(
 // {sum (o-t)^2, sum |o-t|, sum t, sum t^2} per slab of ``rows`` rows;
 // column 0 is bit-identical to fwd_chain_bf16's loss_part. ``pred_out``:
 // caller-owned contiguous fp32 with M elements (may be a view into a
-// larger buffer). Returns (pred or None, part or None). No sync, no host
+// larger buffer). ``task`` = 1 (binary classification, the head value is
+// a logit): part = {sum logloss, sum (sigmoid - t)^2, sum t, sum correct},
+// column 0 bit-identical to fwd_chain_bf16(loss=LOSS_BCE)'s loss_part;
+// with ``hist`` (int64 [2,65536] on x's GPU, caller-owned and persistent)
+// each row also adds 1 to hist[t >= 0.5][key of the logit] with integer
+// atomics — the streaming-AUC histogram (csrc/fwd_chain.hip).
+// Returns (pred or None, part or None). No sync, no host
 // read: graph-capture safe.
 std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>>
 eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
                 const std::vector<at::Tensor>& biases,
                 const c10::optional<at::Tensor>& target,
                 const c10::optional<at::Tensor>& pred_out, bool want_pred,
-                int64_t rows) {
+                int64_t rows, int64_t task,
+                const c10::optional<at::Tensor>& hist) {
   const int crows = chain_rows(rows);
+  const int ctask = chain_loss(task, "eval_chain", "task");
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "eval_chain: x must be contiguous bf16 [M,100]");
@@ -1289,6 +1318,16 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
   } else if (with_pred) {
     pred = at::empty({M}, x.options().dtype(at::kFloat));
   }
+  if (hist.has_value()) {
+    TORCH_CHECK(ctask == kLossBce && target.has_value(),
+                "eval_chain: hist needs task=1 and a target");
+    TORCH_CHECK(hist->is_cuda() && hist->get_device() == x.get_device() &&
+                    hist->scalar_type() == at::kLong &&
+                    hist->is_contiguous() && hist->dim() == 2 &&
+                    hist->size(0) == 2 && hist->size(1) == 65536,
+                "eval_chain: hist must be contiguous int64 [2,65536] on "
+                "x's GPU");
+  }
   const int64_t grid = M > 0 ? fwd_chain_grid(M, crows) : 0;
   if (target.has_value()) {
     part = M > 0 ? at::empty({grid, 4}, x.options().dtype(at::kFloat))
@@ -1306,6 +1345,7 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
         with_pred ? pred.data_ptr<float>() : nullptr,
         target.has_value() ? tgt.data_ptr<float>() : nullptr,
         target.has_value() ? part.data_ptr<float>() : nullptr, M, crows,
+        ctask, hist.has_value() ? hist->data_ptr<int64_t>() : nullptr,
         current_stream());
   }
   c10::optional<at::Tensor> po, pa;
@@ -1375,7 +1415,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("W3"), py::arg("b3"), py::arg("w4"), py::arg("b4"),
         py::arg("target") = c10::nullopt,
         py::arg("xt_out") = c10::nullopt, py::arg("pi16") = false,
-        py::arg("rows") = 0);
+        py::arg("rows") = 0, py::arg("loss") = 0);
   m.def("bwd_chain_bf16", &rsdl::bwd_chain_bf16, py::arg("dy"),
         py::arg("a3"), py::arg("mask1"), py::arg("mask2"), py::arg("w4"),
         py::arg("W3"), py::arg("W2"), py::arg("pi16") = false,
@@ -1388,13 +1428,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_step_bf16", &rsdl::fused_step_bf16, py::arg("x"),
         py::arg("target"), py::arg("weights"), py::arg("biases"),
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
-        py::arg("rows") = 0);
+        py::arg("rows") = 0, py::arg("loss") = 0);
   m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
         py::arg("Wstage"), py::arg("biases"),
         py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,
-        py::arg("want_pred") = true, py::arg("rows") = 0);
+        py::arg("want_pred") = true, py::arg("rows") = 0,
+        py::arg("task") = 0, py::arg("hist") = c10::nullopt);
   m.def("eval_accumulate", &rsdl::eval_accumulate, py::arg("part"),
         py::arg("acc"), py::arg("M"));
+  m.attr("LOSS_MSE") = (int)rsdl::kLossMse;
+  m.attr("LOSS_BCE") = (int)rsdl::kLossBce;
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

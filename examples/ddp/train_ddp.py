@@ -69,6 +69,11 @@ def parse_args():
                    help="compress DDP gradients to fp16 for the RCCL "
                    "allreduce (reference ray_torch_shuffle.py:184-185 "
                    "hvd fp16 compression parity)")
+    p.add_argument("--loss", choices=["mse", "bce"], default="mse",
+                   help="objective of the TabularMLP path (--spec float): "
+                   "mse, or bce = binary cross-entropy with logits on the "
+                   "labels column in [0, 1]; the same choice as "
+                   "models.fused_step.fused_step(loss=)")
     p.add_argument("--device", type=str, default=None)
     return p.parse_args()
 
@@ -157,7 +162,14 @@ def train_main(args, world, rank):
                 None, default_hooks.fp16_compress_hook
             )
     opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9)
-    loss_fn = torch.nn.MSELoss()
+    if args.loss == "bce" and tabular:
+        raise SystemExit("--loss bce is for the TabularMLP path "
+                         "(--spec float)")
+    loss_fn = (
+        torch.nn.functional.binary_cross_entropy_with_logits
+        if args.loss == "bce"
+        else torch.nn.MSELoss()
+    )
 
     import contextlib
 

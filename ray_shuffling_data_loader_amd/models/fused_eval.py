@@ -31,13 +31,31 @@ the training forward's arithmetic and none of its by-products:
   are therefore bf16-ROUNDED (``out`` is bf16); the native path's are the
   unrounded fp32 head values.
 
+``task="binary"`` scores a model trained with ``fused_step(loss="bce")``:
+the head value is a logit o, and with e = exp(-|o|), sg = sigmoid(o) =
+1/(1+e) or e/(1+e) by the sign of o, the four partials become
+{sum l, sum (sg-t)^2, sum t, sum correct}, l = max(o,0) - o*t + log1p(e)
+(the training kernel's expressions) and correct = ((o >= 0) == (t >=
+0.5)); the accumulator then reads {rows, sum logloss, sum brier, sum t,
+n_correct}. A streaming AUC rides in the same kernel: every row adds 1,
+with a 64-bit integer atomic, to a persistent int64 [2][65536] histogram
+at [t >= 0.5][key], key = the top 16 bits of the order-preserving
+transform of the logit's bit pattern (bits ^ 0xFFFFFFFF if negative,
+else bits ^ 0x80000000) — the logit truncated to bf16 precision, order
+kept. Integer adds commute, so the histogram is independent of launch
+and arrival order; it is still three launches per update. compute()
+evaluates the tie-aware Mann-Whitney statistic over the keys in fp64.
+Not handled: a NaN logit lands wherever its bits put it; ``logloss`` is
+then NaN, and that is the signal.
+
 The evaluator reads the parameters and nothing else: it never touches
 ``.grad``, never modifies a parameter and does not depend on
 ``model.training``.
 
 Validated by tests/test_fused_eval_gpu.py (bit-equality with the training
-forward, canaries, accumulator, staging, loader end to end) and
-tests/test_fused_eval_cpu.py (composed path, gloo all-reduce).
+forward, canaries, accumulator, staging, loader end to end),
+tests/test_fused_eval_cpu.py (composed path, gloo all-reduce) and, for
+the binary task, tests/test_fused_bce_gpu.py / tests/test_fused_bce_cpu.py.
 """
 
 import math
@@ -54,6 +72,33 @@ _STAGE_IDX = (0, 1, 2, 5)
 _STAGE_NUMEL = (512 * 112, 256 * 512, 128 * 256, 256 * 512, 128 * 256, 128)
 
 
+_TASKS = {"regression": 0, "binary": 1}
+HIST_BINS = 1 << 16
+
+
+def logit_keys(o: torch.Tensor) -> torch.Tensor:
+    """int64 histogram keys of fp32 logits: the top 16 bits of the
+    order-preserving transform of the bit pattern (the kernel's)."""
+    bits = o.float().contiguous().view(torch.int32).to(torch.int64)
+    bits = bits & 0xFFFFFFFF
+    u = torch.where(bits >> 31 != 0, bits ^ 0xFFFFFFFF, bits ^ 0x80000000)
+    return u >> 16
+
+
+def auc_from_hist(hist: torch.Tensor) -> float:
+    """Tie-aware Mann-Whitney AUC of an int64 [2, bins] histogram
+    (row 0 negatives, row 1 positives, keys ascending with the score), in
+    fp64: sum_b pos[b] * (neg_below[b] + neg[b] / 2) / (P * N). NaN when
+    either class is absent."""
+    neg = hist[0].double()
+    pos = hist[1].double()
+    n_pos, n_neg = pos.sum().item(), neg.sum().item()
+    if n_pos <= 0 or n_neg <= 0:
+        return float("nan")
+    below = torch.cumsum(neg, 0) - neg
+    return (pos * (below + 0.5 * neg)).sum().item() / (n_pos * n_neg)
+
+
 def _check_x(x: torch.Tensor) -> None:
     """Reject what the training step's bindings reject, in their words."""
     if not (x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 100
@@ -65,7 +110,7 @@ def _check_x(x: torch.Tensor) -> None:
 
 
 class FusedEvaluator:
-    """Streaming regression metrics of ``model`` over loader batches.
+    """Streaming metrics of ``model`` over loader batches.
 
     ``update(x, target)`` folds one batch into an on-device fp64
     accumulator (three launches at steady state on the native path, no
@@ -74,12 +119,27 @@ class FusedEvaluator:
     ``predict(x)`` returns the fp32 [M,1] predictions of the same forward.
     ``rows`` is the chain kernels' slab size (32 or 64; 0 = the default of
     fused_step / the extension); it regroups the partial sums only.
+
+    ``task="binary"``: the predictions are logits (``predict`` is
+    unchanged), the accumulator is {rows, sum logloss, sum brier, sum t,
+    n_correct} and ``compute()`` returns ``{"rows", "logloss", "accuracy",
+    "brier", "base_rate", "auc"}``. ``auc=False`` drops the histogram (none
+    is allocated or written) and the key.
     """
 
-    def __init__(self, model: TabularMLP, rows: int = 0):
+    def __init__(self, model: TabularMLP, rows: int = 0,
+                 task: str = "regression", auc: bool = True):
+        if task not in _TASKS:
+            raise ValueError(
+                "FusedEvaluator: task must be 'regression' or 'binary', "
+                f"got {task!r}")
         self.model = model
         self._lin = _fs._layers(model)
         self.rows = int(rows)
+        self.task = task
+        self._binary = task == "binary"
+        self.auc = bool(auc) and self._binary
+        self._hist: Optional[torch.Tensor] = None
         self._acc: Optional[torch.Tensor] = None
         self._bufs = None
         self._stage_key = None
@@ -114,6 +174,18 @@ class FusedEvaluator:
         if self._acc is None or self._acc.device != device:
             self._acc = torch.zeros(5, dtype=torch.float64, device=device)
         return self._acc
+
+    def _histogram(self, device) -> Optional[torch.Tensor]:
+        if not self.auc:
+            return None
+        if self._hist is None or self._hist.device != device:
+            self._hist = torch.zeros(2, HIST_BINS, dtype=torch.int64,
+                                     device=device)
+        return self._hist
+
+    def _native_ok_task(self, hip) -> bool:
+        # the binary task needs the extension's task/hist arguments
+        return not self._binary or hasattr(hip, "LOSS_BCE")
 
     def _stage(self, hip):
         """[W1s, W2s, W3s, w4b], re-staged with one step_prep launch when
@@ -179,18 +251,42 @@ class FusedEvaluator:
             return
         hip = self._hip()
         acc = self._accumulator(x.device)
+        hist = self._histogram(x.device)
         if target.dtype not in (torch.float32, torch.float64):
             target = target.float()
-        if self._native_ok(hip, x) and target.is_cuda:
+        if (self._native_ok(hip, x) and target.is_cuda
+                and self._native_ok_task(hip)):
+            kw = self._rows_kw()
+            if self._binary:
+                kw["task"] = 1
+                if hist is not None:
+                    kw["hist"] = hist
             _, part = hip.eval_chain_bf16(
                 x, self._stage(hip), self._biases(), target=target,
-                want_pred=False, **self._rows_kw(),
+                want_pred=False, **kw,
             )
             hip.eval_accumulate(part, acc, M)
             return
-        o = self._composed_out(hip, x).reshape(-1).double()
+        out = self._composed_out(hip, x).reshape(-1)
+        o = out.double()
         # the kernels read the target as fp32
         t = target.reshape(-1).float().double().to(o.device)
+        if self._binary:
+            e = torch.exp(-o.abs())
+            sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+            ll = torch.clamp(o, min=0.0) - o * t + torch.log1p(e)
+            cls = t >= 0.5
+            acc += torch.stack([
+                torch.full((), float(M), dtype=torch.float64,
+                           device=o.device),
+                ll.sum(), ((sg - t) ** 2).sum(), t.sum(),
+                ((o >= 0) == cls).double().sum(),
+            ])
+            if hist is not None:
+                idx = cls.to(torch.int64) * HIST_BINS + logit_keys(out)
+                hist += torch.bincount(
+                    idx, minlength=2 * HIST_BINS).view(2, HIST_BINS)
+            return
         d = o - t
         acc += torch.stack([
             torch.full((), float(M), dtype=torch.float64, device=o.device),
@@ -200,10 +296,24 @@ class FusedEvaluator:
     def reset(self) -> None:
         if self._acc is not None:
             self._acc.zero_()
+        if self._hist is not None:
+            self._hist.zero_()
+
+    def hist_state(self) -> Optional[torch.Tensor]:
+        """A copy of the int64 [2, 65536] AUC histogram (row 0 negatives,
+        row 1 positives; on the device), or None when the evaluator keeps
+        none (regression task, ``auc=False``)."""
+        if not self.auc:
+            return None
+        if self._hist is None:
+            return torch.zeros(2, HIST_BINS, dtype=torch.int64,
+                               device=self._lin[0].weight.device)
+        return self._hist.clone()
 
     def state(self) -> torch.Tensor:
         """A copy of the fp64 accumulator {rows, sse, sae, sum_t, sum_tt}
-        (on the device; reading it is the caller's sync)."""
+        — {rows, sum logloss, sum brier, sum_t, n_correct} for the binary
+        task — (on the device; reading it is the caller's sync)."""
         if self._acc is None:
             # no batch yet: zeros where the model lives, so a collective
             # over the ranks' states still finds a tensor of its backend
@@ -216,15 +326,36 @@ class FusedEvaluator:
         metrics. With torch.distributed initialised, or ``group`` given, a
         copy of the five sums is SUM-all-reduced first, so every rank
         returns the metrics of all ranks' rows. Zero rows give NaN
-        metrics."""
+        metrics. The binary task returns {"rows", "logloss", "accuracy",
+        "brier", "base_rate"} and, unless ``auc=False``, "auc" (its
+        histogram is all-reduced the same way; NaN when a class is
+        absent)."""
         v = self.state()
+        h = self.hist_state()
         import torch.distributed as dist
 
         if group is not None or (dist.is_available()
                                  and dist.is_initialized()):
             dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
+            if h is not None:
+                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
         rows, sse, sae, st, stt = v.tolist()
         nan = float("nan")
+        if self._binary:
+            if rows <= 0:
+                res = {"rows": 0, "logloss": nan, "accuracy": nan,
+                       "brier": nan, "base_rate": nan}
+            else:
+                res = {
+                    "rows": int(rows),
+                    "logloss": sse / rows,
+                    "accuracy": stt / rows,
+                    "brier": sae / rows,
+                    "base_rate": st / rows,
+                }
+            if h is not None:
+                res["auc"] = auc_from_hist(h)
+            return res
         if rows <= 0:
             return {"rows": 0, "mse": nan, "rmse": nan, "mae": nan,
                     "r2": nan}

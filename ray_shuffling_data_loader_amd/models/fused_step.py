@@ -7,8 +7,9 @@ and no copy:
   1. step_prep: fp32 master weights -> bf16 fragment-major W1s (K padded
      to 112), W2s, W3s, W2^T s, W3^T s, bf16 w4, fp32 target
   2. x swizzle (emits both x layouts)
-  3. fwd chain (3 MFMA layers + head + MSE loss/grad; emits a1^T/a2^T
-     wgrad fragments + relu-mask words)
+  3. fwd chain (3 MFMA layers + head + loss/grad, MSE or binary
+     cross-entropy with logits; emits a1^T/a2^T wgrad fragments +
+     relu-mask words)
   4. bwd chain (dgrad chain from mask bits; emits dz^T fragments + db/dW4
      partials)
   5-7. three fragment-major wgrad kernels into per-slab partials
@@ -96,6 +97,33 @@ def _weight_buffers(model: TabularMLP, lin):
     return buf
 
 
+# loss= of fused_step -> the chain kernels' compile-time selector
+# (LOSS_MSE / LOSS_BCE of the extension). The loss enters the schedule in
+# the forward chain's head epilogue only: everything after it is linear
+# in dy, and step_finalize divides the summed partials by M either way.
+_LOSSES = {"mse": 0, "bce": 1}
+
+
+def _loss_kw(code: int) -> dict:
+    """``loss=`` for the bindings; empty for MSE, as _rows_kw is at its
+    default, so stand-ins that predate the argument stay callable."""
+    return {"loss": code} if code else {}
+
+
+def bce_head(out: torch.Tensor, target: torch.Tensor, m_rows: int):
+    """(dyb bf16 [M,1], loss_part fp32 [1]) of the BCE head in torch,
+    from the chain's bf16 ``out`` and with the kernel's formulas — for
+    stand-ins without LOSS_BCE (FakeHip forms its MSE head from the bf16
+    ``out`` the same way)."""
+    o = out.float().reshape(-1, 1)
+    t = target.float().reshape(-1, 1)
+    e = torch.exp(-o.abs())
+    sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    dyb = ((1.0 / m_rows) * (sg - t)).bfloat16()
+    part = (torch.clamp(o, min=0.0) - o * t + torch.log1p(e)).sum()
+    return dyb, part.reshape(1)
+
+
 def _rows_kw() -> dict:
     """``rows=`` for the chain bindings; empty at the default, which also
     keeps the call valid for stand-ins that predate the argument."""
@@ -137,12 +165,17 @@ def _flat_outs(lin):
 
 def fused_step(
     model: TabularMLP, x: torch.Tensor, target: torch.Tensor,
-    grad_hook=None,
+    grad_hook=None, loss: str = "mse",
 ) -> Tuple[torch.Tensor, None]:
-    """One manual fwd+bwd: computes the MSE loss and POPULATES .grad on
+    """One manual fwd+bwd: computes the loss and POPULATES .grad on
     every parameter of ``model`` (fp32, ready for an optimizer step).
     ``x`` is the bf16 [M,100] feature batch; ``target`` is [M,1].
     Returns the (scalar fp32) loss.
+
+    ``loss``: "mse" (default), or "bce" — binary cross-entropy with
+    logits, mean over the batch; the model's output is the logit and
+    ``target`` any value in [0, 1] (soft labels allowed; no pos-weight,
+    no sample weights).
 
     ``grad_hook`` (flat-grad DP mode): called as grads become ready —
     ``grad_hook("bias")`` once every bias grad AND the head weight grad
@@ -150,6 +183,10 @@ def fused_step(
     wgrad kernels), then ``grad_hook("w1"|"w2"|"w3")`` after each weight
     grad copy. Lets the caller overlap per-slice gradient collectives
     with the remaining wgrad kernels (bench RSDL_OVERLAP_ALLREDUCE)."""
+    if loss not in _LOSSES:
+        raise ValueError(
+            f"fused_step: loss must be 'mse' or 'bce', got {loss!r}")
+    loss_code = _LOSSES[loss]
     from ray_shuffling_data_loader_amd.ops.shuffle_ops import _load_hip
 
     hip = _load_hip()
@@ -165,7 +202,7 @@ def fused_step(
                 x, target,
                 [m.weight.detach() for m in lin],
                 [m.bias.detach() for m in lin],
-                pi16=_PI16, outs=outs, **_rows_kw(),
+                pi16=_PI16, outs=outs, **_rows_kw(), **_loss_kw(loss_code),
             )
             if outs is None:
                 # dW1..dW4 then db1..db4, fresh fp32 tensors in the
@@ -184,10 +221,21 @@ def fused_step(
     mchunks = 2 * ((M + 31) // 32)
     xt = torch.empty(4 * mchunks * 512, dtype=torch.bfloat16,
                      device=x.device)
-    a1t, mask1, a2t, mask2, a3, out, dyb, loss_part = hip.fwd_chain_bf16(
-        x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"], b4,
-        target=target, xt_out=xt, pi16=_PI16, **_rows_kw(),
-    )
+    if loss_code and not hasattr(hip, "LOSS_BCE"):
+        # a stand-in without the BCE head: forward only, head in torch
+        a1t, mask1, a2t, mask2, a3, out = hip.fwd_chain_bf16(
+            x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"], b4,
+            target=None, xt_out=xt, pi16=_PI16, **_rows_kw(),
+        )
+        dyb, loss_part = bce_head(out, target, M)
+    else:
+        a1t, mask1, a2t, mask2, a3, out, dyb, loss_part = (
+            hip.fwd_chain_bf16(
+                x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"],
+                b4, target=target, xt_out=xt, pi16=_PI16, **_rows_kw(),
+                **_loss_kw(loss_code),
+            )
+        )
     loss = loss_part.sum() / M
     # Backward chain: consumes the masks (never the activations), emits
     # dz^T fragments; dW4/db4 partials fold into its seed loop.
