@@ -61,7 +61,8 @@
 // and tests/test_chain_sim.py (lane-level index simulation); the
 // forward-only eval_chain_kernel by tests/test_fused_eval_gpu.py; the BCE
 // head, the binary task and the AUC histogram by
-// tests/test_fused_bce_gpu.py.
+// tests/test_fused_bce_gpu.py; the weighted heads (sample weights,
+// pos_weight, fixed-point histogram) by tests/test_fused_weights_gpu.py.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -372,6 +373,25 @@ __device__ __forceinline__ void fc_bce_terms(float o, float t, float& sg,
   l = fmaxf(o, 0.f) - o * t + log1pf(e);
 }
 
+// The pos_weight form of the logistic head (p != 1), torch's definition:
+// l = p t softplus(-o) + (1-t) softplus(o), softplus(+-o) = max(+-o, 0) +
+// log1p(e) with the same overflow-free e, and g = dl/do = (1-t) sg -
+// p t (1-sg). 1-sg is formed as sigmoid(-o) from the same e (the other of
+// the two quotients), not by subtraction: sg rounds to 1 from o ~ 17, and
+// the positive rows' gradient must not vanish with it.
+__device__ __forceinline__ void fc_bce_pw_terms(float o, float t, float p,
+                                                float& sg, float& l,
+                                                float& g) {
+  const float e = expf(-fabsf(o));
+  const float big = 1.f / (1.f + e), small = e / (1.f + e);
+  sg = o >= 0.f ? big : small;
+  const float cs = o >= 0.f ? small : big;  // 1 - sg
+  const float lp = log1pf(e);
+  const float pt = p * t;
+  l = pt * (fmaxf(-o, 0.f) + lp) + (1.f - t) * (fmaxf(o, 0.f) + lp);
+  g = (1.f - t) * sg - pt * cs;
+}
+
 // Loss selector of fwd_chain_kernel / task selector of eval_chain_kernel
 // (exported by the binding as LOSS_MSE / LOSS_BCE).
 #define FC_LOSS_MSE 0
@@ -394,9 +414,19 @@ __device__ __forceinline__ int32_t fc_fresh_lane(int32_t lane) {
 // LOSS picks the head epilogue only (FC_LOSS_MSE: dyb = 2/M (o-t), terms
 // (o-t)^2; FC_LOSS_BCE: dyb = 1/M (sigmoid(o)-t), terms from
 // fc_bce_terms); the layers, the LDS plan and the barriers do not see it.
-template <int MT, bool PI16, int LOSS = FC_LOSS_MSE>
-__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
-fwd_chain_kernel(
+// WEIGHTED (the fwd_chain_w_kernel entry points; the unweighted ones
+// pass false and compile to what they did before the flag existed): the
+// head also takes ``weight`` (fp32 [M], read under the m0 + m < M guard
+// only; null = every w is 1) and ``pos_weight`` p, normalisation still by
+// M. MSE: dyb = bf16((2/M w)(o-t)), terms w (o-t)^2. BCE, p == 1: dyb =
+// bf16((w/M)(sg-t)), terms w l. BCE, p != 1 (a workgroup-uniform branch;
+// torch's definition): l = p t softplus(-o) + (1-t) softplus(o) with
+// softplus(+-o) = max(+-o, 0) + log1p(exp(-|o|)), dl/do = (1-t) sg -
+// p t (1-sg), 1-sg taken as sigmoid(-o). The grouping makes w = 1, p = 1
+// reproduce the unweighted bits; a row with w = 0 gives dyb = +-0 and a
+// zero term.
+template <int MT, bool PI16, int LOSS, bool WEIGHTED>
+__device__ __forceinline__ void fc_fwd_chain_body(
     const short* __restrict__ x0s,  // fragment-major swizzled x (see note)
     const short* __restrict__ W1, const float* __restrict__ b1,
     const short* __restrict__ W2, const float* __restrict__ b2,
@@ -413,7 +443,7 @@ fwd_chain_kernel(
     // chain from the fused train step. BCE: see LOSS above.
     const float* __restrict__ target, short* __restrict__ dyb,
     float* __restrict__ loss_part, float inv_m, int64_t M,
-    int64_t mchunks) {
+    int64_t mchunks, const float* __restrict__ weight, float pos_weight) {
   // LDS budget is the occupancy lever. x needs no tile (pre-swizzled
   // fragment-major in global, coalesced A loads), and a1 itself leaves
   // through the EMIT_T epilogue, transposed, plus mask words — no
@@ -489,15 +519,35 @@ fwd_chain_kernel(
       if (m0 + m < M) {
         out[m0 + m] = fc_f2b(o);
         if (target != nullptr) {
-          if (LOSS == FC_LOSS_MSE) {
-            const float diff = o - target[m0 + m];
-            dyb[m0 + m] = fc_f2b(2.f * inv_m * diff);
-            d2 = diff * diff;
+          if (!WEIGHTED) {
+            if (LOSS == FC_LOSS_MSE) {
+              const float diff = o - target[m0 + m];
+              dyb[m0 + m] = fc_f2b(2.f * inv_m * diff);
+              d2 = diff * diff;
+            } else {
+              float sg;
+              const float t = target[m0 + m];
+              fc_bce_terms(o, t, sg, d2);
+              dyb[m0 + m] = fc_f2b(inv_m * (sg - t));
+            }
           } else {
-            float sg;
+            const float w = weight != nullptr ? weight[m0 + m] : 1.f;
             const float t = target[m0 + m];
-            fc_bce_terms(o, t, sg, d2);
-            dyb[m0 + m] = fc_f2b(inv_m * (sg - t));
+            if (LOSS == FC_LOSS_MSE) {
+              const float diff = o - t;
+              dyb[m0 + m] = fc_f2b((2.f * inv_m * w) * diff);
+              d2 = w * (diff * diff);
+            } else if (pos_weight == 1.f) {
+              float sg, l;
+              fc_bce_terms(o, t, sg, l);
+              dyb[m0 + m] = fc_f2b((inv_m * w) * (sg - t));
+              d2 = w * l;
+            } else {
+              float sg, l, g;
+              fc_bce_pw_terms(o, t, pos_weight, sg, l, g);
+              dyb[m0 + m] = fc_f2b((inv_m * w) * g);
+              d2 = w * l;
+            }
           }
         }
       }
@@ -515,6 +565,45 @@ fwd_chain_kernel(
   }
 
   fc_store_tile<MT, FC_N3, FC_S3>(t3, a3, m0, M, tid);
+}
+
+template <int MT, bool PI16, int LOSS = FC_LOSS_MSE>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+fwd_chain_kernel(
+    const short* __restrict__ x0s, const short* __restrict__ W1,
+    const float* __restrict__ b1, const short* __restrict__ W2,
+    const float* __restrict__ b2, const short* __restrict__ W3,
+    const float* __restrict__ b3, const short* __restrict__ w4,
+    const float* __restrict__ b4, short* __restrict__ a1t,
+    uint32_t* __restrict__ mask1, short* __restrict__ a2t,
+    uint32_t* __restrict__ mask2, short* __restrict__ a3,
+    short* __restrict__ out, const float* __restrict__ target,
+    short* __restrict__ dyb, float* __restrict__ loss_part, float inv_m,
+    int64_t M, int64_t mchunks) {
+  fc_fwd_chain_body<MT, PI16, LOSS, false>(
+      x0s, W1, b1, W2, b2, W3, b3, w4, b4, a1t, mask1, a2t, mask2, a3, out,
+      target, dyb, loss_part, inv_m, M, mchunks, nullptr, 1.f);
+}
+
+// The weighted head (sample weights and/or pos_weight); launched only when
+// the caller passes either, so the default step runs fwd_chain_kernel.
+template <int MT, bool PI16, int LOSS>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+fwd_chain_w_kernel(
+    const short* __restrict__ x0s, const short* __restrict__ W1,
+    const float* __restrict__ b1, const short* __restrict__ W2,
+    const float* __restrict__ b2, const short* __restrict__ W3,
+    const float* __restrict__ b3, const short* __restrict__ w4,
+    const float* __restrict__ b4, short* __restrict__ a1t,
+    uint32_t* __restrict__ mask1, short* __restrict__ a2t,
+    uint32_t* __restrict__ mask2, short* __restrict__ a3,
+    short* __restrict__ out, const float* __restrict__ target,
+    short* __restrict__ dyb, float* __restrict__ loss_part, float inv_m,
+    int64_t M, int64_t mchunks, const float* __restrict__ weight,
+    float pos_weight) {
+  fc_fwd_chain_body<MT, PI16, LOSS, true>(
+      x0s, W1, b1, W2, b2, W3, b3, w4, b4, a1t, mask1, a2t, mask2, a3, out,
+      target, dyb, loss_part, inv_m, M, mchunks, weight, pos_weight);
 }
 
 // Forward-only sibling of fwd_chain_kernel for evaluation
@@ -541,9 +630,20 @@ fwd_chain_kernel(
 // kept): the streaming-AUC histogram. Integer atomics commute, so the
 // histogram does not depend on launch or arrival order. A NaN logit lands
 // wherever its bits put it. ``hist`` is ignored by the regression task.
-template <int MT, int TASK = FC_LOSS_MSE>
-__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
-eval_chain_kernel(
+// WEIGHTED (the eval_chain_w_kernel entry points; the unweighted ones
+// compile to what they did before the flag existed): ``weight`` (fp32 [M],
+// read under the m0 + m < M guard only; null = every w is 1) scales every
+// term and a fifth partial carries the weight sum, in rows of EIGHT floats
+// (two aligned float4 for eval_accumulate; columns 5-7 are written as 0):
+//   regression  {sum w d^2, sum w |d|, sum w t, sum w t^2, sum w, 0, 0, 0}
+//   binary      {sum w l, sum w (sg-t)^2, sum w t, sum w correct, sum w, ..}
+// Column 0 is loss_part of the weighted training kernel at pos_weight = 1
+// (the same w * term expressions, the same serial sum). The histogram add
+// becomes llrintf(w * 2^20), a fixed-point weight with quantum 2^-20 —
+// still integer atomics, still independent of arrival order. Negative or
+// non-finite weights are undefined.
+template <int MT, int TASK, bool WEIGHTED>
+__device__ __forceinline__ void fc_eval_chain_body(
     const short* __restrict__ x0s,  // fragment-major swizzled x
     const short* __restrict__ W1, const float* __restrict__ b1,
     const short* __restrict__ W2, const float* __restrict__ b2,
@@ -551,20 +651,24 @@ eval_chain_kernel(
     const short* __restrict__ w4, const float* __restrict__ b4,
     float* __restrict__ pred, const float* __restrict__ target,
     float* __restrict__ part, int64_t M, int64_t mchunks,
-    unsigned long long* __restrict__ hist) {
+    unsigned long long* __restrict__ hist,
+    const float* __restrict__ weight) {
   // LDS plan of fwd_chain_kernel, with four lsum columns instead of one
-  // (MT = 1: 50.7 KB, 3 workgroups/CU; MT = 2: 67.6 KB, 2 workgroups/CU).
+  // (MT = 1: 50.7 KB, 3 workgroups/CU; MT = 2: 67.6 KB, 2 workgroups/CU);
+  // five when WEIGHTED (MT = 1: 50,816 B; MT = 2: 67,840 B = 66.25 KB,
+  // under half of the CU's 160 KB, so still 2 workgroups/CU).
+  constexpr int NCOL = WEIGHTED ? 5 : 4;
   constexpr int ROWS = MT * FC_MT;
   constexpr int T1B = ROWS * FC_S1 * 2;
   constexpr int T2B = ROWS * FC_S2 * 2;
   constexpr int TILEB = MT == 1 ? T1B + T2B : T1B;
   static_assert(MT == 1 || T2B + ROWS * FC_S3 * 2 <= T1B, "t2+t3 in t1");
-  __shared__ __align__(16) char smem[TILEB + 4 * ROWS * 4];
+  __shared__ __align__(16) char smem[TILEB + NCOL * ROWS * 4];
   short* t1 = reinterpret_cast<short*>(smem);
   short* t2 = reinterpret_cast<short*>(MT == 1 ? smem + T1B : smem);
   // aliased: live ranges are disjoint (barrier-ordered)
   short* t3 = reinterpret_cast<short*>(MT == 1 ? smem : smem + T2B);
-  float* lsum = reinterpret_cast<float*>(smem + TILEB);  // [4][ROWS]
+  float* lsum = reinterpret_cast<float*>(smem + TILEB);  // [NCOL][ROWS]
 
   const int64_t m0 = (int64_t)blockIdx.x * ROWS;
   const int32_t tid = threadIdx.x;
@@ -605,11 +709,12 @@ eval_chain_kernel(
     }
     if (prt == 0) {
       const float o = s + b4[0];
-      float d2 = 0.f, ad = 0.f, t = 0.f, c3 = 0.f;
+      float d2 = 0.f, ad = 0.f, t = 0.f, c3 = 0.f, w = 0.f;
       if (m0 + m < M) {
         if (pred != nullptr) pred[m0 + m] = o;
         if (target != nullptr) {
           t = target[m0 + m];
+          if (WEIGHTED) w = weight != nullptr ? weight[m0 + m] : 1.f;
           if (TASK == FC_LOSS_MSE) {
             const float diff = o - t;
             d2 = diff * diff;
@@ -625,29 +730,82 @@ eval_chain_kernel(
               const uint32_t bits = __float_as_uint(o);
               const uint32_t u =
                   bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-              atomicAdd(&hist[(cls ? 65536u : 0u) + (u >> 16)], 1ULL);
+              atomicAdd(&hist[(cls ? 65536u : 0u) + (u >> 16)],
+                        WEIGHTED ? (unsigned long long)llrintf(
+                                       w * 1048576.f)
+                                 : 1ULL);
             }
           }
         }
       }
       if (target != nullptr) {
-        lsum[m] = d2;
-        lsum[ROWS + m] = ad;
-        lsum[2 * ROWS + m] = t;
-        lsum[3 * ROWS + m] = TASK == FC_LOSS_MSE ? t * t : c3;
+        if (!WEIGHTED) {
+          lsum[m] = d2;
+          lsum[ROWS + m] = ad;
+          lsum[2 * ROWS + m] = t;
+          lsum[3 * ROWS + m] = TASK == FC_LOSS_MSE ? t * t : c3;
+        } else {
+          // rows past M have w = 0 and zero terms: every product is +0
+          lsum[m] = w * d2;
+          lsum[ROWS + m] = w * ad;
+          lsum[2 * ROWS + m] = w * t;
+          lsum[3 * ROWS + m] = w * (TASK == FC_LOSS_MSE ? t * t : c3);
+          lsum[4 * ROWS + m] = w;
+        }
       }
     }
   }
   if (target != nullptr) {
     __syncthreads();
-    if (tid < 4) {
-      const float* col = lsum + tid * ROWS;
+    if (!WEIGHTED) {
+      if (tid < 4) {
+        const float* col = lsum + tid * ROWS;
+        float s = 0.f;
+        #pragma unroll
+        for (int32_t m = 0; m < ROWS; m++) s += col[m];
+        part[(int64_t)blockIdx.x * 4 + tid] = s;
+      }
+    } else if (tid < 8) {
       float s = 0.f;
-      #pragma unroll
-      for (int32_t m = 0; m < ROWS; m++) s += col[m];
-      part[(int64_t)blockIdx.x * 4 + tid] = s;
+      if (tid < NCOL) {
+        const float* col = lsum + tid * ROWS;
+        #pragma unroll
+        for (int32_t m = 0; m < ROWS; m++) s += col[m];
+      }
+      part[(int64_t)blockIdx.x * 8 + tid] = s;
     }
   }
+}
+
+template <int MT, int TASK = FC_LOSS_MSE>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+eval_chain_kernel(
+    const short* __restrict__ x0s, const short* __restrict__ W1,
+    const float* __restrict__ b1, const short* __restrict__ W2,
+    const float* __restrict__ b2, const short* __restrict__ W3,
+    const float* __restrict__ b3, const short* __restrict__ w4,
+    const float* __restrict__ b4, float* __restrict__ pred,
+    const float* __restrict__ target, float* __restrict__ part, int64_t M,
+    int64_t mchunks, unsigned long long* __restrict__ hist) {
+  fc_eval_chain_body<MT, TASK, false>(x0s, W1, b1, W2, b2, W3, b3, w4, b4,
+                                      pred, target, part, M, mchunks, hist,
+                                      nullptr);
+}
+
+template <int MT, int TASK>
+__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
+eval_chain_w_kernel(
+    const short* __restrict__ x0s, const short* __restrict__ W1,
+    const float* __restrict__ b1, const short* __restrict__ W2,
+    const float* __restrict__ b2, const short* __restrict__ W3,
+    const float* __restrict__ b3, const short* __restrict__ w4,
+    const float* __restrict__ b4, float* __restrict__ pred,
+    const float* __restrict__ target, float* __restrict__ part, int64_t M,
+    int64_t mchunks, unsigned long long* __restrict__ hist,
+    const float* __restrict__ weight) {
+  fc_eval_chain_body<MT, TASK, true>(x0s, W1, b1, W2, b2, W3, b3, w4, b4,
+                                     pred, target, part, M, mchunks, hist,
+                                     weight);
 }
 
 // x [M,100] bf16 -> fragment-major [ceil(M/32)][7][2][32][8] with zero
@@ -872,6 +1030,48 @@ void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
                      target ? 1.f / (float)M : 0.f, M, mchunks);
 }
 
+// The weighted head: ``weight`` fp32 [M] or null (every w = 1),
+// ``pos_weight`` > 0 (BCE only; the binding rejects it for MSE). ``target``
+// must not be null. The binding comes here only when a weight or a
+// pos_weight != 1 was given.
+void launch_fwd_chain_w(const void* x0s, const void* W1, const float* b1,
+                        const void* W2, const float* b2, const void* W3,
+                        const float* b3, const void* w4, const float* b4,
+                        void* a1t, uint32_t* mask1, void* a2t,
+                        uint32_t* mask2, void* a3, void* out,
+                        const float* target, void* dyb, float* loss_part,
+                        int64_t M, int pi16, int rows, int loss,
+                        const float* weight, float pos_weight,
+                        hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
+  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
+  auto kern = rows == 64
+      ? (pi16 ? fwd_chain_w_kernel<2, true, FC_LOSS_MSE>
+              : fwd_chain_w_kernel<2, false, FC_LOSS_MSE>)
+      : (pi16 ? fwd_chain_w_kernel<1, true, FC_LOSS_MSE>
+              : fwd_chain_w_kernel<1, false, FC_LOSS_MSE>);
+  if (loss == FC_LOSS_BCE) {
+    kern = rows == 64
+        ? (pi16 ? fwd_chain_w_kernel<2, true, FC_LOSS_BCE>
+                : fwd_chain_w_kernel<2, false, FC_LOSS_BCE>)
+        : (pi16 ? fwd_chain_w_kernel<1, true, FC_LOSS_BCE>
+                : fwd_chain_w_kernel<1, false, FC_LOSS_BCE>);
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+                     stream,
+                     reinterpret_cast<const short*>(x0s),
+                     reinterpret_cast<const short*>(W1), b1,
+                     reinterpret_cast<const short*>(W2), b2,
+                     reinterpret_cast<const short*>(W3), b3,
+                     reinterpret_cast<const short*>(w4), b4,
+                     reinterpret_cast<short*>(a1t), mask1,
+                     reinterpret_cast<short*>(a2t), mask2,
+                     reinterpret_cast<short*>(a3),
+                     reinterpret_cast<short*>(out), target,
+                     reinterpret_cast<short*>(dyb), loss_part,
+                     1.f / (float)M, M, mchunks, weight, pos_weight);
+}
+
 // Forward-only evaluation chain: ``pred`` (fp32 [M]) and/or ``target``
 // with ``part`` (fp32 [fwd_chain_grid(M, rows), 4]); either may be null.
 // ``task`` = FC_LOSS_MSE (regression partials) or FC_LOSS_BCE (binary
@@ -898,6 +1098,33 @@ void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
                      reinterpret_cast<const short*>(w4), b4, pred, target,
                      part, M, mchunks,
                      reinterpret_cast<unsigned long long*>(hist));
+}
+
+// Weighted evaluation chain: ``target`` and ``part`` (fp32 [grid, 8]) are
+// required, ``weight`` fp32 [M] or null (every w = 1).
+void launch_eval_chain_w(const void* x0s, const void* W1, const float* b1,
+                         const void* W2, const float* b2, const void* W3,
+                         const float* b3, const void* w4, const float* b4,
+                         float* pred, const float* target, float* part,
+                         int64_t M, int rows, int task, int64_t* hist,
+                         const float* weight, hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
+  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
+  auto kern = rows == 64 ? eval_chain_w_kernel<2, FC_LOSS_MSE>
+                         : eval_chain_w_kernel<1, FC_LOSS_MSE>;
+  if (task == FC_LOSS_BCE) {
+    kern = rows == 64 ? eval_chain_w_kernel<2, FC_LOSS_BCE>
+                      : eval_chain_w_kernel<1, FC_LOSS_BCE>;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+                     stream,
+                     reinterpret_cast<const short*>(x0s),
+                     reinterpret_cast<const short*>(W1), b1,
+                     reinterpret_cast<const short*>(W2), b2,
+                     reinterpret_cast<const short*>(W3), b3,
+                     reinterpret_cast<const short*>(w4), b4, pred, target,
+                     part, M, mchunks,
+                     reinterpret_cast<unsigned long long*>(hist), weight);
 }
 
 }  // namespace rsdl

@@ -11,6 +11,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <tuple>
@@ -121,6 +122,21 @@ void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
                        float* pred, const float* target, float* part,
                        int64_t M, int rows, int task, int64_t* hist,
                        hipStream_t stream);
+void launch_fwd_chain_w(const void* x0s, const void* W1, const float* b1,
+                        const void* W2, const float* b2, const void* W3,
+                        const float* b3, const void* w4, const float* b4,
+                        void* a1t, uint32_t* mask1, void* a2t,
+                        uint32_t* mask2, void* a3, void* out,
+                        const float* target, void* dyb, float* loss_part,
+                        int64_t M, int pi16, int rows, int loss,
+                        const float* weight, float pos_weight,
+                        hipStream_t stream);
+void launch_eval_chain_w(const void* x0s, const void* W1, const float* b1,
+                         const void* W2, const float* b2, const void* W3,
+                         const float* b3, const void* w4, const float* b4,
+                         float* pred, const float* target, float* part,
+                         int64_t M, int rows, int task, int64_t* hist,
+                         const float* weight, hipStream_t stream);
 int64_t bwd_chain_grid(int64_t M, int rows);
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
@@ -694,6 +710,39 @@ static int chain_loss(int64_t loss, const char* who, const char* what) {
   return static_cast<int>(loss);
 }
 
+// Sample weights and pos_weight of the fused head (csrc/fwd_chain.hip),
+// validated for ``who``: ``weight`` fp32 [M] on x's GPU or absent (every
+// w = 1), ``pos_weight`` finite and > 0, and != 1 only with LOSS_BCE.
+// ``on`` says whether the weighted kernel is needed at all: with no weight
+// and pos_weight == 1 the bindings launch what they always launched.
+struct HeadWeights {
+  bool on = false;
+  const float* weight = nullptr;
+  float pos_weight = 1.f;
+};
+
+static HeadWeights head_weights(const char* who, const at::Tensor& x,
+                                const c10::optional<at::Tensor>& weight,
+                                double pos_weight, int loss) {
+  HeadWeights h;
+  TORCH_CHECK(std::isfinite(pos_weight) && pos_weight > 0.0, who,
+              ": pos_weight must be finite and > 0, got ", pos_weight);
+  TORCH_CHECK(pos_weight == 1.0 || loss == kLossBce, who,
+              ": pos_weight needs loss=1 (BCE)");
+  if (weight.has_value()) {
+    TORCH_CHECK(weight->is_cuda() &&
+                    weight->get_device() == x.get_device() &&
+                    weight->scalar_type() == at::kFloat &&
+                    weight->is_contiguous() && weight->numel() == x.size(0),
+                who, ": weight must be contiguous fp32 with ", x.size(0),
+                " elements on x's GPU");
+    h.weight = weight->data_ptr<float>();
+  }
+  h.pos_weight = static_cast<float>(pos_weight);
+  h.on = weight.has_value() || h.pos_weight != 1.f;
+  return h;
+}
+
 // Buffers + launches of the forward chain, shared by fwd_chain_bf16 and
 // fused_step_bf16. Weights arrive fragment-major (W1 with K padded to
 // 112), biases fp32, ``tgt`` fp32 [M] or nullptr. Nothing is launched for
@@ -708,7 +757,8 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
                           const at::Tensor& b2f, const at::Tensor& b3f,
                           const at::Tensor& b4f, const at::Tensor* tgt,
                           const c10::optional<at::Tensor>& xt_out,
-                          bool pi16, int rows, int loss) {
+                          bool pi16, int rows, int loss,
+                          const HeadWeights& hw = HeadWeights()) {
   FwdChainOut f;
   const int64_t M = x.size(0);
   // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
@@ -751,16 +801,30 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
     } else {
       launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
     }
-    launch_fwd_chain(
-        xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
-        W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
-        b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
-        f.a1t.data_ptr(),
-        reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
-        f.a2t.data_ptr(),
-        reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
-        f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
-        pi16 ? 1 : 0, rows, loss, current_stream());
+    if (hw.on && tgt_ptr != nullptr) {
+      launch_fwd_chain_w(
+          xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
+          W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
+          b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
+          f.a1t.data_ptr(),
+          reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
+          f.a2t.data_ptr(),
+          reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
+          f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
+          pi16 ? 1 : 0, rows, loss, hw.weight, hw.pos_weight,
+          current_stream());
+    } else {
+      launch_fwd_chain(
+          xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
+          W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
+          b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
+          f.a1t.data_ptr(),
+          reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
+          f.a2t.data_ptr(),
+          reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
+          f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
+          pi16 ? 1 : 0, rows, loss, current_stream());
+    }
   }
   return f;
 }
@@ -771,9 +835,15 @@ std::vector<at::Tensor> fwd_chain_bf16(
     const at::Tensor& b3, const at::Tensor& w4, const at::Tensor& b4,
     const c10::optional<at::Tensor>& target,
     const c10::optional<at::Tensor>& xt_out, bool pi16, int64_t rows,
-    int64_t loss) {
+    int64_t loss, const c10::optional<at::Tensor>& weight,
+    double pos_weight) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fwd_chain", "loss");
+  // Sample weights / pos_weight of the loss epilogue (need a target).
+  const HeadWeights hw =
+      head_weights("fwd_chain", x, weight, pos_weight, closs);
+  TORCH_CHECK(!hw.on || target.has_value(),
+              "fwd_chain: weight / pos_weight need a target");
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fwd_chain: x must be contiguous bf16 [M,100]");
@@ -822,7 +892,7 @@ std::vector<at::Tensor> fwd_chain_bf16(
   }
   auto f = run_fwd_chain(x, W1s, W2s, W3s, w4, b1f, b2f, b3f, b4f,
                          with_loss ? &tgt : nullptr, xt_out, pi16, crows,
-                         closs);
+                         closs, hw);
   if (with_loss) {
     return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out, f.dyb,
             f.loss_part};
@@ -1203,9 +1273,12 @@ std::vector<at::Tensor> fused_step_bf16(
     const std::vector<at::Tensor>& weights,
     const std::vector<at::Tensor>& biases, bool pi16,
     const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
-    int64_t loss) {
+    int64_t loss, const c10::optional<at::Tensor>& weight,
+    double pos_weight) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fused_step", "loss");
+  const HeadWeights hw =
+      head_weights("fused_step", x, weight, pos_weight, closs);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
               "fused_step: x must be contiguous bf16 [M,100]");
@@ -1227,7 +1300,7 @@ std::vector<at::Tensor> fused_step_bf16(
       at::empty({4 * mchunks * 512}, x.options());
   auto f = run_fwd_chain(x, pr.W1s, pr.W2s, pr.W3s, pr.w4b, biases[0],
                          biases[1], biases[2], biases[3], &pr.tgt, xt, pi16,
-                         crows, closs);
+                         crows, closs, hw);
   auto b = run_bwd_chain(f.dyb, f.a3, f.mask1, f.mask2, pr.w4b, pr.W3Ts,
                          pr.W2Ts, pi16, crows);
   // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
@@ -1255,6 +1328,9 @@ std::vector<at::Tensor> fused_step_bf16(
 // with ``hist`` (int64 [2,65536] on x's GPU, caller-owned and persistent)
 // each row also adds 1 to hist[t >= 0.5][key of the logit] with integer
 // atomics — the streaming-AUC histogram (csrc/fwd_chain.hip).
+// ``weight`` (fp32 [M] on x's GPU, needs a target): the weighted kernel —
+// every term scaled by w, part fp32 [grid, 8] = {the four sums, sum w, 0,
+// 0, 0}, and the histogram adds llrintf(w * 2^20) in place of 1.
 // Returns (pred or None, part or None). No sync, no host
 // read: graph-capture safe.
 std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>>
@@ -1263,7 +1339,8 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
                 const c10::optional<at::Tensor>& target,
                 const c10::optional<at::Tensor>& pred_out, bool want_pred,
                 int64_t rows, int64_t task,
-                const c10::optional<at::Tensor>& hist) {
+                const c10::optional<at::Tensor>& hist,
+                const c10::optional<at::Tensor>& weight) {
   const int crows = chain_rows(rows);
   const int ctask = chain_loss(task, "eval_chain", "task");
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
@@ -1328,25 +1405,44 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
                 "eval_chain: hist must be contiguous int64 [2,65536] on "
                 "x's GPU");
   }
+  // ``weight`` (fp32 [M]): the weighted kernel, part fp32 [grid, 8] =
+  // {the four sums with every term scaled by w, sum w, 0, 0, 0}, and the
+  // histogram adds llrintf(w * 2^20) in place of 1.
+  TORCH_CHECK(!weight.has_value() || target.has_value(),
+              "eval_chain: weight needs a target");
+  const HeadWeights hw = head_weights("eval_chain", x, weight, 1.0, ctask);
+  const int64_t pcols = hw.on ? 8 : 4;
   const int64_t grid = M > 0 ? fwd_chain_grid(M, crows) : 0;
   if (target.has_value()) {
-    part = M > 0 ? at::empty({grid, 4}, x.options().dtype(at::kFloat))
-                 : at::zeros({1, 4}, x.options().dtype(at::kFloat));
+    part = M > 0 ? at::empty({grid, pcols}, x.options().dtype(at::kFloat))
+                 : at::zeros({1, pcols}, x.options().dtype(at::kFloat));
   }
   if (M > 0) {
     const int64_t Mp = (M + 31) / 32 * 32;
     auto xs = at::empty({Mp * 112}, x.options());
     launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
-    launch_eval_chain(
-        xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
-        Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
-        Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
-        Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
-        with_pred ? pred.data_ptr<float>() : nullptr,
-        target.has_value() ? tgt.data_ptr<float>() : nullptr,
-        target.has_value() ? part.data_ptr<float>() : nullptr, M, crows,
-        ctask, hist.has_value() ? hist->data_ptr<int64_t>() : nullptr,
-        current_stream());
+    if (hw.on) {
+      launch_eval_chain_w(
+          xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
+          Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
+          Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
+          Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
+          with_pred ? pred.data_ptr<float>() : nullptr,
+          tgt.data_ptr<float>(), part.data_ptr<float>(), M, crows, ctask,
+          hist.has_value() ? hist->data_ptr<int64_t>() : nullptr, hw.weight,
+          current_stream());
+    } else {
+      launch_eval_chain(
+          xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
+          Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
+          Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
+          Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
+          with_pred ? pred.data_ptr<float>() : nullptr,
+          target.has_value() ? tgt.data_ptr<float>() : nullptr,
+          target.has_value() ? part.data_ptr<float>() : nullptr, M, crows,
+          ctask, hist.has_value() ? hist->data_ptr<int64_t>() : nullptr,
+          current_stream());
+    }
   }
   c10::optional<at::Tensor> po, pa;
   if (with_pred) po = pred;
@@ -1356,23 +1452,26 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
 
 // acc[5] = {rows, sse, sae, sum_t, sum_tt} (fp64, persistent) += M and
 // the column sums of ``part`` [n, 4], in place, one launch, fixed order
-// (csrc/step_glue.hip).
+// (csrc/step_glue.hip). The weighted chain's ``part`` [n, 8] folds into
+// acc[6] = {rows, c0..c3, sum w} the same way.
 void eval_accumulate(const at::Tensor& part, const at::Tensor& acc,
                      int64_t M) {
   TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat &&
                   part.is_contiguous() && part.dim() == 2 &&
-                  part.size(1) == 4 &&
+                  (part.size(1) == 4 || part.size(1) == 8) &&
                   reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
               "eval_accumulate: part must be contiguous aligned fp32 [n,4] "
-              "on GPU");
+              "(or [n,8], weighted) on GPU");
+  const bool wide = part.size(1) == 8;
   TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kDouble &&
-                  acc.is_contiguous() && acc.numel() == 5 &&
+                  acc.is_contiguous() && acc.numel() == (wide ? 6 : 5) &&
                   acc.get_device() == part.get_device(),
-              "eval_accumulate: acc must be contiguous fp64 [5] on part's "
-              "GPU");
+              "eval_accumulate: acc must be contiguous fp64 [",
+              wide ? 6 : 5, "] on part's GPU");
   TORCH_CHECK(M >= 0, "eval_accumulate: M must not be negative");
   launch_eval_accumulate(part.data_ptr<float>(), part.size(0), M,
-                         acc.data_ptr<double>(), current_stream());
+                         acc.data_ptr<double>(), wide ? 5 : 4,
+                         current_stream());
 }
 
 }  // namespace rsdl
@@ -1415,7 +1514,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("W3"), py::arg("b3"), py::arg("w4"), py::arg("b4"),
         py::arg("target") = c10::nullopt,
         py::arg("xt_out") = c10::nullopt, py::arg("pi16") = false,
-        py::arg("rows") = 0, py::arg("loss") = 0);
+        py::arg("rows") = 0, py::arg("loss") = 0,
+        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0);
   m.def("bwd_chain_bf16", &rsdl::bwd_chain_bf16, py::arg("dy"),
         py::arg("a3"), py::arg("mask1"), py::arg("mask2"), py::arg("w4"),
         py::arg("W3"), py::arg("W2"), py::arg("pi16") = false,
@@ -1428,16 +1528,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_step_bf16", &rsdl::fused_step_bf16, py::arg("x"),
         py::arg("target"), py::arg("weights"), py::arg("biases"),
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
-        py::arg("rows") = 0, py::arg("loss") = 0);
+        py::arg("rows") = 0, py::arg("loss") = 0,
+        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0);
   m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
         py::arg("Wstage"), py::arg("biases"),
         py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,
         py::arg("want_pred") = true, py::arg("rows") = 0,
-        py::arg("task") = 0, py::arg("hist") = c10::nullopt);
+        py::arg("task") = 0, py::arg("hist") = c10::nullopt,
+        py::arg("weight") = c10::nullopt);
   m.def("eval_accumulate", &rsdl::eval_accumulate, py::arg("part"),
         py::arg("acc"), py::arg("M"));
   m.attr("LOSS_MSE") = (int)rsdl::kLossMse;
   m.attr("LOSS_BCE") = (int)rsdl::kLossBce;
+  // the heads take sample weights / pos_weight (weight=, pos_weight=)
+  m.attr("HEAD_WEIGHTS") = 1;
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

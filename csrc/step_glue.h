@@ -43,8 +43,10 @@ struct StepFinArgs {
 
 void launch_step_prep(const StepPrepArgs& p, hipStream_t stream);
 void launch_step_finalize(const StepFinArgs& p, hipStream_t stream);
-// part fp32 [nrows, 4] (16-byte aligned) -> acc fp64 [5] += {M, column sums}
+// ncol = 4: part fp32 [nrows, 4] (16-byte aligned) -> acc fp64 [5] +=
+// {M, column sums}; ncol = 5: part fp32 [nrows, 8] (columns 0..4 used) ->
+// acc fp64 [6]
 void launch_eval_accumulate(const float* part, int64_t nrows, int64_t M,
-                            double* acc, hipStream_t stream);
+                            double* acc, int ncol, hipStream_t stream);
 
 }  // namespace rsdl

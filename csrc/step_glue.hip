@@ -362,41 +362,55 @@ void launch_step_finalize(const StepFinArgs& p, hipStream_t stream) {
 // totals and M into acc. No atomics, no zero fill, no host read: the same
 // partials in the same order give the same bits, and the launch can be
 // captured in a graph.
+//
+// NC = 5: the weighted chain's partials, rows of eight floats {c0..c3,
+// sum w, 0, 0, 0}, fold into acc[6] = {rows, c0..c3, sum w} the same way
+// (the second float4 of a row carries column 4). NC = 4 is the layout and
+// the summation order above, unchanged.
 // ---------------------------------------------------------------------
+template <int NC>
 __global__ void __launch_bounds__(256) eval_accumulate_kernel(
     const float* __restrict__ part, int64_t nrows, int64_t M,
     double* __restrict__ acc) {
-  __shared__ double lds[4][256];
+  static_assert(NC == 4 || NC == 5, "4 or 5 partial columns");
+  constexpr int V = NC == 4 ? 1 : 2;  // float4 per partial row
+  __shared__ double lds[NC][256];
   const int32_t tid = threadIdx.x;
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  double a[NC];
+  #pragma unroll
+  for (int e = 0; e < NC; e++) a[e] = 0.0;
   // unrolled so several loads are in flight; the add order is unchanged
   #pragma unroll 4
   for (int64_t r = tid; r < nrows; r += 256) {
-    const sg_f32x4 v = reinterpret_cast<const sg_f32x4*>(part)[r];
+    const sg_f32x4 v = reinterpret_cast<const sg_f32x4*>(part)[r * V];
     #pragma unroll
     for (int e = 0; e < 4; e++) a[e] += (double)v[e];
+    if (NC == 5) a[NC - 1] += (double)part[r * 8 + 4];
   }
   #pragma unroll
-  for (int e = 0; e < 4; e++) lds[e][tid] = a[e];
+  for (int e = 0; e < NC; e++) lds[e][tid] = a[e];
   __syncthreads();
   for (int32_t d = 128; d > 0; d >>= 1) {
     if (tid < d) {
       #pragma unroll
-      for (int e = 0; e < 4; e++) lds[e][tid] += lds[e][tid + d];
+      for (int e = 0; e < NC; e++) lds[e][tid] += lds[e][tid + d];
     }
     __syncthreads();
   }
   if (tid == 0) {
     acc[0] += (double)M;
     #pragma unroll
-    for (int e = 0; e < 4; e++) acc[1 + e] += lds[e][0];
+    for (int e = 0; e < NC; e++) acc[1 + e] += lds[e][0];
   }
 }
 
+// ``ncol`` = 4 (part [nrows, 4], acc [5]) or 5 (part [nrows, 8], acc [6]).
 void launch_eval_accumulate(const float* part, int64_t nrows, int64_t M,
-                            double* acc, hipStream_t stream) {
-  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(256), 0, stream,
-                     part, nrows, M, acc);
+                            double* acc, int ncol, hipStream_t stream) {
+  auto kern = ncol == 5 ? eval_accumulate_kernel<5>
+                        : eval_accumulate_kernel<4>;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, stream, part, nrows, M,
+                     acc);
 }
 
 }  // namespace rsdl

@@ -74,6 +74,16 @@ def parse_args():
                    "mse, or bce = binary cross-entropy with logits on the "
                    "labels column in [0, 1]; the same choice as "
                    "models.fused_step.fused_step(loss=)")
+    p.add_argument("--weight-column", type=str, default=None,
+                   metavar="NAME",
+                   help="per-row sample-weight column of the files "
+                   "(TabularMLP path, --spec float): batches become "
+                   "(features, label, weight) and the loss is weighted, "
+                   "mean over the batch — the same choice as "
+                   "fused_step(sample_weight=)")
+    p.add_argument("--pos-weight", type=float, default=None, metavar="P",
+                   help="positive-class weight of --loss bce (TabularMLP "
+                   "path) — the same choice as fused_step(pos_weight=)")
     p.add_argument("--device", type=str, default=None)
     return p.parse_args()
 
@@ -148,6 +158,7 @@ def train_main(args, world, rank):
             feature_columns=feature_columns,
             label_column="labels",
             feature_matrix=True,
+            weight_column=args.weight_column,
             device=device,
         )
         model = TabularMLP(args.num_cols).to(device)
@@ -165,11 +176,27 @@ def train_main(args, world, rank):
     if args.loss == "bce" and tabular:
         raise SystemExit("--loss bce is for the TabularMLP path "
                          "(--spec float)")
-    loss_fn = (
-        torch.nn.functional.binary_cross_entropy_with_logits
-        if args.loss == "bce"
-        else torch.nn.MSELoss()
+    if tabular and (args.weight_column or args.pos_weight is not None):
+        raise SystemExit("--weight-column / --pos-weight are for the "
+                         "TabularMLP path (--spec float)")
+    if args.pos_weight is not None and args.loss != "bce":
+        raise SystemExit("--pos-weight needs --loss bce")
+    pos_weight = (
+        None if args.pos_weight is None
+        else torch.tensor([args.pos_weight], device=device)
     )
+
+    def loss_fn(out, target, weight=None):
+        """Mean over the batch of the (weighted) per-row loss: what
+        fused_step(loss=, sample_weight=, pos_weight=) minimises."""
+        if weight is not None:
+            weight = weight.reshape(-1, 1)
+        if args.loss == "bce":
+            return torch.nn.functional.binary_cross_entropy_with_logits(
+                out, target, weight=weight, pos_weight=pos_weight)
+        if weight is None:
+            return torch.nn.functional.mse_loss(out, target)
+        return (weight * (out - target) ** 2).mean()
 
     import contextlib
 
@@ -190,14 +217,18 @@ def train_main(args, world, rank):
             else contextlib.nullcontext()
         )
         with join_ctx:
-            for data, target in ds:
+            for batch in ds:
+                # (features, label) or, with --weight-column, a third
+                # member: the [B] sample weight
+                data, target = batch[0], batch[1]
+                weight = batch[2] if len(batch) == 3 else None
                 wait_times.append(time.perf_counter() - t_wait)
                 if args.mock_train_step_time is not None:
                     time.sleep(args.mock_train_step_time)
                 else:
                     x = data if tabular else data[0]
                     opt.zero_grad(set_to_none=True)
-                    loss = loss_fn(model(x), target)
+                    loss = loss_fn(model(x), target, weight)
                     loss.backward()
                     opt.step()
                 n_batches += 1

@@ -48,6 +48,14 @@ evaluates the tie-aware Mann-Whitney statistic over the keys in fp64.
 Not handled: a NaN logit lands wherever its bits put it; ``logloss`` is
 then NaN, and that is the signal.
 
+``weighted=True`` scores with per-row sample weights w (those of
+``fused_step(sample_weight=)``): the weighted chain kernel scales every
+term by w and carries a fifth partial, sum w; the accumulator has six
+entries {rows, c0..c3, sum w} and every mean is divided by sum w, not by
+the row count. The histogram then adds llrint(w * 2^20) in place of 1 — a
+fixed-point weight, so the adds stay integer and order-independent, and
+the AUC, being scale-invariant, needs no change.
+
 The evaluator reads the parameters and nothing else: it never touches
 ``.grad``, never modifies a parameter and does not depend on
 ``model.training``.
@@ -55,7 +63,9 @@ The evaluator reads the parameters and nothing else: it never touches
 Validated by tests/test_fused_eval_gpu.py (bit-equality with the training
 forward, canaries, accumulator, staging, loader end to end),
 tests/test_fused_eval_cpu.py (composed path, gloo all-reduce) and, for
-the binary task, tests/test_fused_bce_gpu.py / tests/test_fused_bce_cpu.py.
+the binary task, tests/test_fused_bce_gpu.py / tests/test_fused_bce_cpu.py;
+the weighted metrics by tests/test_fused_weights_gpu.py /
+tests/test_fused_weights_cpu.py.
 """
 
 import math
@@ -74,6 +84,8 @@ _STAGE_NUMEL = (512 * 112, 256 * 512, 128 * 256, 256 * 512, 128 * 256, 128)
 
 _TASKS = {"regression": 0, "binary": 1}
 HIST_BINS = 1 << 16
+# Fixed-point scale of a weighted histogram count: llrint(w * 2^20).
+HIST_WEIGHT_SCALE = float(1 << 20)
 
 
 def logit_keys(o: torch.Tensor) -> torch.Tensor:
@@ -125,10 +137,28 @@ class FusedEvaluator:
     n_correct} and ``compute()`` returns ``{"rows", "logloss", "accuracy",
     "brier", "base_rate", "auc"}``. ``auc=False`` drops the histogram (none
     is allocated or written) and the key.
+
+    ``weighted=True``: ``update(x, target, sample_weight)`` requires the
+    per-row weights ([M] or [M,1], any float dtype, cast to fp32), the
+    accumulator is fp64 [6] = {rows, c0..c3, sum w}, and ``compute()``
+    divides every mean by sum w: ``mse``, ``rmse``, ``mae`` and ``r2`` =
+    1 - sum w d^2 / (sum w t^2 - (sum w t)^2 / sum w), or ``logloss``,
+    ``accuracy``, ``brier``, ``base_rate`` and the weighted ``auc``.
+    ``rows`` stays the row count and ``"weight_sum"`` is added; sum w <= 0
+    gives NaN metrics. With ``weighted=False`` (default) nothing changes
+    and passing ``sample_weight`` raises.
+
+    Weighted AUC histogram: each row adds llrint(w * 2^20) to its int64
+    bin, a fixed-point representation of the weight. The quantum is 2^-20
+    (weights that are multiples of it are represented exactly, smaller
+    ones round to nearest, ties to even); the capacity is 2^43 units of
+    total weight per bin (2^63 / 2^20). Negative or non-finite weights are
+    undefined and are not checked, because a check would need a sync.
     """
 
     def __init__(self, model: TabularMLP, rows: int = 0,
-                 task: str = "regression", auc: bool = True):
+                 task: str = "regression", auc: bool = True,
+                 weighted: bool = False):
         if task not in _TASKS:
             raise ValueError(
                 "FusedEvaluator: task must be 'regression' or 'binary', "
@@ -139,6 +169,8 @@ class FusedEvaluator:
         self.task = task
         self._binary = task == "binary"
         self.auc = bool(auc) and self._binary
+        self.weighted = bool(weighted)
+        self._nacc = 6 if self.weighted else 5
         self._hist: Optional[torch.Tensor] = None
         self._acc: Optional[torch.Tensor] = None
         self._bufs = None
@@ -172,7 +204,8 @@ class FusedEvaluator:
 
     def _accumulator(self, device) -> torch.Tensor:
         if self._acc is None or self._acc.device != device:
-            self._acc = torch.zeros(5, dtype=torch.float64, device=device)
+            self._acc = torch.zeros(self._nacc, dtype=torch.float64,
+                                    device=device)
         return self._acc
 
     def _histogram(self, device) -> Optional[torch.Tensor]:
@@ -184,7 +217,10 @@ class FusedEvaluator:
         return self._hist
 
     def _native_ok_task(self, hip) -> bool:
-        # the binary task needs the extension's task/hist arguments
+        # the binary task needs the extension's task/hist arguments, the
+        # weighted metrics its weighted heads
+        if self.weighted and not getattr(hip, "HEAD_WEIGHTS", 0):
+            return False
         return not self._binary or hasattr(hip, "LOSS_BCE")
 
     def _stage(self, hip):
@@ -238,8 +274,11 @@ class FusedEvaluator:
             return pred.view(M, 1)
         return self._composed_out(hip, x).float().reshape(M, 1)
 
-    def update(self, x: torch.Tensor, target: torch.Tensor) -> None:
-        """Fold one batch into the accumulator. Never syncs."""
+    def update(self, x: torch.Tensor, target: torch.Tensor,
+               sample_weight: Optional[torch.Tensor] = None) -> None:
+        """Fold one batch into the accumulator. Never syncs.
+        ``sample_weight``: required with ``weighted=True``, refused
+        otherwise."""
         _check_x(x)
         M = x.shape[0]
         if target.numel() != M:
@@ -247,6 +286,19 @@ class FusedEvaluator:
                 f"fused_eval: target size mismatch ({target.numel()} "
                 f"values for {M} rows)"
             )
+        if self.weighted:
+            if sample_weight is None:
+                raise ValueError(
+                    "fused_eval: weighted=True needs update(x, target, "
+                    "sample_weight)")
+            if sample_weight.numel() != M:
+                raise ValueError(
+                    f"fused_eval: sample_weight has {sample_weight.numel()}"
+                    f" values for {M} rows")
+        elif sample_weight is not None:
+            raise ValueError(
+                "fused_eval: sample_weight needs "
+                "FusedEvaluator(weighted=True)")
         if M == 0:
             return
         hip = self._hip()
@@ -254,9 +306,18 @@ class FusedEvaluator:
         hist = self._histogram(x.device)
         if target.dtype not in (torch.float32, torch.float64):
             target = target.float()
+        w32 = None
+        if self.weighted:
+            w32 = sample_weight.reshape(-1)
+            if w32.dtype != torch.float32:
+                w32 = w32.float()
+            w32 = w32.contiguous()
         if (self._native_ok(hip, x) and target.is_cuda
-                and self._native_ok_task(hip)):
+                and self._native_ok_task(hip)
+                and (w32 is None or w32.device == x.device)):
             kw = self._rows_kw()
+            if w32 is not None:
+                kw["weight"] = w32
             if self._binary:
                 kw["task"] = 1
                 if hist is not None:
@@ -271,6 +332,10 @@ class FusedEvaluator:
         o = out.double()
         # the kernels read the target as fp32
         t = target.reshape(-1).float().double().to(o.device)
+        if self.weighted:
+            self._composed_weighted(acc, hist, out, o, t,
+                                    w32.to(o.device), M)
+            return
         if self._binary:
             e = torch.exp(-o.abs())
             sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
@@ -293,6 +358,33 @@ class FusedEvaluator:
             (d * d).sum(), d.abs().sum(), t.sum(), (t * t).sum(),
         ])
 
+    def _composed_weighted(self, acc, hist, out, o, t, w32, M) -> None:
+        """The weighted kernel's sums in fp64 torch: every term scaled by
+        w (the fp32 weight, widened), a sixth sum for w, and the histogram
+        fed with llrint(w * 2^20) formed in fp32 as the kernel forms it."""
+        w = w32.double()
+        rows = torch.full((), float(M), dtype=torch.float64,
+                          device=o.device)
+        if not self._binary:
+            d = o - t
+            acc += torch.stack([
+                rows, (w * d * d).sum(), (w * d.abs()).sum(), (w * t).sum(),
+                (w * t * t).sum(), w.sum(),
+            ])
+            return
+        e = torch.exp(-o.abs())
+        sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+        ll = torch.clamp(o, min=0.0) - o * t + torch.log1p(e)
+        cls = t >= 0.5
+        acc += torch.stack([
+            rows, (w * ll).sum(), (w * (sg - t) ** 2).sum(), (w * t).sum(),
+            (w * ((o >= 0) == cls).double()).sum(), w.sum(),
+        ])
+        if hist is not None:
+            idx = cls.to(torch.int64) * HIST_BINS + logit_keys(out)
+            units = torch.round(w32 * HIST_WEIGHT_SCALE).to(torch.int64)
+            hist.view(-1).index_add_(0, idx, units)
+
     def reset(self) -> None:
         if self._acc is not None:
             self._acc.zero_()
@@ -313,19 +405,23 @@ class FusedEvaluator:
     def state(self) -> torch.Tensor:
         """A copy of the fp64 accumulator {rows, sse, sae, sum_t, sum_tt}
         — {rows, sum logloss, sum brier, sum_t, n_correct} for the binary
-        task — (on the device; reading it is the caller's sync)."""
+        task — (on the device; reading it is the caller's sync). With
+        ``weighted=True`` every sum is weighted and a sixth entry holds
+        sum w."""
         if self._acc is None:
             # no batch yet: zeros where the model lives, so a collective
             # over the ranks' states still finds a tensor of its backend
-            return torch.zeros(5, dtype=torch.float64,
+            return torch.zeros(self._nacc, dtype=torch.float64,
                                device=self._lin[0].weight.device)
         return self._acc.clone()
 
     def compute(self, group=None) -> Dict[str, float]:
         """Read the accumulator back (the one host read) and derive the
         metrics. With torch.distributed initialised, or ``group`` given, a
-        copy of the five sums is SUM-all-reduced first, so every rank
-        returns the metrics of all ranks' rows. Zero rows give NaN
+        copy of the five sums (six with ``weighted=True``, whose means are
+        over sum w and whose result gains "weight_sum") is SUM-all-reduced
+        first, so every rank returns the metrics of all ranks' rows. Zero
+        rows give NaN
         metrics. The binary task returns {"rows", "logloss", "accuracy",
         "brier", "base_rate"} and, unless ``auc=False``, "auc" (its
         histogram is all-reduced the same way; NaN when a class is
@@ -339,8 +435,10 @@ class FusedEvaluator:
             dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
             if h is not None:
                 dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
-        rows, sse, sae, st, stt = v.tolist()
         nan = float("nan")
+        if self.weighted:
+            return self._weighted_metrics(v.tolist(), h)
+        rows, sse, sae, st, stt = v.tolist()
         if self._binary:
             if rows <= 0:
                 res = {"rows": 0, "logloss": nan, "accuracy": nan,
@@ -368,6 +466,32 @@ class FusedEvaluator:
             "mae": sae / rows,
             "r2": 1.0 - sse / den if den != 0.0 else nan,
         }
+
+    def _weighted_metrics(self, v, h) -> Dict[str, float]:
+        """compute() for ``weighted=True``: the means over sum w."""
+        rows, c0, c1, c2, c3, sw = v
+        nan = float("nan")
+        ok = sw > 0.0
+        res = {"rows": int(rows), "weight_sum": sw}
+        if self._binary:
+            res.update({
+                "logloss": c0 / sw if ok else nan,
+                "accuracy": c3 / sw if ok else nan,
+                "brier": c1 / sw if ok else nan,
+                "base_rate": c2 / sw if ok else nan,
+            })
+            if h is not None:
+                res["auc"] = auc_from_hist(h)
+            return res
+        mse = c0 / sw if ok else nan
+        den = c3 - c2 * c2 / sw if ok else 0.0
+        res.update({
+            "mse": mse,
+            "rmse": math.sqrt(mse) if ok else nan,
+            "mae": c1 / sw if ok else nan,
+            "r2": 1.0 - c0 / den if ok and den != 0.0 else nan,
+        })
+        return res
 
 
 def fused_predict(model: TabularMLP, x: torch.Tensor) -> torch.Tensor:

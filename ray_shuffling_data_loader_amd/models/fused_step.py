@@ -8,7 +8,8 @@ and no copy:
      to 112), W2s, W3s, W2^T s, W3^T s, bf16 w4, fp32 target
   2. x swizzle (emits both x layouts)
   3. fwd chain (3 MFMA layers + head + loss/grad, MSE or binary
-     cross-entropy with logits; emits a1^T/a2^T wgrad fragments +
+     cross-entropy with logits, optionally with per-row sample weights
+     and a positive-class weight; emits a1^T/a2^T wgrad fragments +
      relu-mask words)
   4. bwd chain (dgrad chain from mask bits; emits dz^T fragments + db/dW4
      partials)
@@ -124,6 +125,81 @@ def bce_head(out: torch.Tensor, target: torch.Tensor, m_rows: int):
     return dyb, part.reshape(1)
 
 
+def loss_head(out: torch.Tensor, target: torch.Tensor, m_rows: int,
+              loss: str = "bce", sample_weight=None, pos_weight=None):
+    """(dyb bf16 [M,1], loss_part fp32 [1]) of the weighted head in torch,
+    from the chain's bf16 ``out`` and with the kernel's formulas and
+    grouping (csrc/fwd_chain.hip, WEIGHTED) — for stand-ins without
+    HEAD_WEIGHTS. ``sample_weight`` fp32 [M] or None (every w = 1),
+    ``pos_weight`` a float or None (BCE only). Normalisation is by M.
+    With w = 1 and no pos_weight the results are those of ``bce_head`` /
+    the stand-in's own MSE head, bit for bit."""
+    o = out.float().reshape(-1, 1)
+    t = target.float().reshape(-1, 1).to(o.device)
+    inv_m = torch.tensor(1.0 / m_rows, dtype=torch.float32, device=o.device)
+    if sample_weight is None:
+        w = torch.ones_like(o)
+    else:
+        w = sample_weight.float().reshape(-1, 1).to(o.device)
+    if loss == "mse":
+        diff = o - t
+        dyb = ((2.0 * inv_m * w) * diff).bfloat16()
+        return dyb, (w * (diff * diff)).sum().reshape(1)
+    e = torch.exp(-o.abs())
+    big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+    sg = torch.where(o >= 0, big, small)
+    if pos_weight is None or float(pos_weight) == 1.0:
+        g = sg - t
+        term = torch.clamp(o, min=0.0) - o * t + torch.log1p(e)
+    else:
+        pt = float(pos_weight) * t
+        lp = torch.log1p(e)
+        term = (pt * (torch.clamp(-o, min=0.0) + lp)
+                + (1.0 - t) * (torch.clamp(o, min=0.0) + lp))
+        # 1 - sg as sigmoid(-o), as the kernel forms it
+        g = (1.0 - t) * sg - pt * torch.where(o >= 0, small, big)
+    dyb = ((inv_m * w) * g).bfloat16()
+    return dyb, (w * term).sum().reshape(1)
+
+
+def _head_args(M: int, loss: str, sample_weight, pos_weight):
+    """Validated (fp32 [M] weight or None, pos_weight float or None) of
+    fused_step; a pos_weight of exactly 1 is no pos_weight."""
+    if pos_weight is not None:
+        if loss != "bce":
+            raise ValueError(
+                "fused_step: pos_weight needs loss='bce', got "
+                f"loss={loss!r}")
+        pos_weight = float(pos_weight)
+        if not (pos_weight > 0.0 and pos_weight != float("inf")):
+            raise ValueError(
+                "fused_step: pos_weight must be finite and > 0, got "
+                f"{pos_weight!r}")
+        if pos_weight == 1.0:
+            pos_weight = None
+    if sample_weight is not None:
+        if sample_weight.numel() != M:
+            raise ValueError(
+                f"fused_step: sample_weight has {sample_weight.numel()} "
+                f"values for {M} rows")
+        sample_weight = sample_weight.reshape(-1)
+        if sample_weight.dtype != torch.float32:
+            sample_weight = sample_weight.float()
+        sample_weight = sample_weight.contiguous()
+    return sample_weight, pos_weight
+
+
+def _weight_kw(sample_weight, pos_weight) -> dict:
+    """``weight=`` / ``pos_weight=`` for the bindings; empty when neither
+    is given, so stand-ins that predate the arguments stay callable."""
+    kw = {}
+    if sample_weight is not None:
+        kw["weight"] = sample_weight
+    if pos_weight is not None:
+        kw["pos_weight"] = pos_weight
+    return kw
+
+
 def _rows_kw() -> dict:
     """``rows=`` for the chain bindings; empty at the default, which also
     keeps the call valid for stand-ins that predate the argument."""
@@ -165,7 +241,8 @@ def _flat_outs(lin):
 
 def fused_step(
     model: TabularMLP, x: torch.Tensor, target: torch.Tensor,
-    grad_hook=None, loss: str = "mse",
+    grad_hook=None, loss: str = "mse", sample_weight=None,
+    pos_weight=None,
 ) -> Tuple[torch.Tensor, None]:
     """One manual fwd+bwd: computes the loss and POPULATES .grad on
     every parameter of ``model`` (fp32, ready for an optimizer step).
@@ -174,8 +251,17 @@ def fused_step(
 
     ``loss``: "mse" (default), or "bce" — binary cross-entropy with
     logits, mean over the batch; the model's output is the logit and
-    ``target`` any value in [0, 1] (soft labels allowed; no pos-weight,
-    no sample weights).
+    ``target`` any value in [0, 1] (soft labels allowed).
+
+    ``sample_weight``: per-row weights w, [M] or [M,1] in any float dtype
+    (cast to fp32 once if needed). The loss is ``(w * l).sum() / M`` —
+    normalised by M, as ``reduction="mean"`` with ``weight=`` in torch, not
+    by the weight sum; pre-scale the weights for that. ``pos_weight``
+    (BCE only): a Python float p > 0 multiplying the positive term,
+    l = p t softplus(-o) + (1-t) softplus(o), as
+    ``F.binary_cross_entropy_with_logits(pos_weight=)``. Both enter in the
+    forward chain's head epilogue only; without them the step launches
+    exactly what it always launched.
 
     ``grad_hook`` (flat-grad DP mode): called as grads become ready —
     ``grad_hook("bias")`` once every bias grad AND the head weight grad
@@ -187,14 +273,21 @@ def fused_step(
         raise ValueError(
             f"fused_step: loss must be 'mse' or 'bce', got {loss!r}")
     loss_code = _LOSSES[loss]
+    M = x.shape[0]
+    loss_name = loss
+    sample_weight, pos_weight = _head_args(M, loss, sample_weight,
+                                           pos_weight)
+    weighted = sample_weight is not None or pos_weight is not None
     from ray_shuffling_data_loader_amd.ops.shuffle_ops import _load_hip
 
     hip = _load_hip()
     lin = _layers(model)
-    M = x.shape[0]
+    has_weights = bool(getattr(hip, "HEAD_WEIGHTS", 0))
     from ray_shuffling_data_loader_amd.ops.shuffle_ops import wgrad_frag
 
-    if _native_ok(hip, lin, x, target, grad_hook):
+    if _native_ok(hip, lin, x, target, grad_hook) and (
+            not weighted or (has_weights and (
+                sample_weight is None or sample_weight.device == x.device))):
         flat_mode = getattr(model, "_rsdl_flat_grads", False)
         outs = _flat_outs(lin) if flat_mode else None
         if not flat_mode or outs is not None:
@@ -203,6 +296,7 @@ def fused_step(
                 [m.weight.detach() for m in lin],
                 [m.bias.detach() for m in lin],
                 pi16=_PI16, outs=outs, **_rows_kw(), **_loss_kw(loss_code),
+                **_weight_kw(sample_weight, pos_weight),
             )
             if outs is None:
                 # dW1..dW4 then db1..db4, fresh fp32 tensors in the
@@ -221,19 +315,29 @@ def fused_step(
     mchunks = 2 * ((M + 31) // 32)
     xt = torch.empty(4 * mchunks * 512, dtype=torch.bfloat16,
                      device=x.device)
-    if loss_code and not hasattr(hip, "LOSS_BCE"):
-        # a stand-in without the BCE head: forward only, head in torch
+    if (loss_code and not hasattr(hip, "LOSS_BCE")) or (
+            weighted and not has_weights):
+        # a stand-in without the BCE head or without the weighted heads:
+        # forward only, head in torch
         a1t, mask1, a2t, mask2, a3, out = hip.fwd_chain_bf16(
             x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"], b4,
             target=None, xt_out=xt, pi16=_PI16, **_rows_kw(),
         )
-        dyb, loss_part = bce_head(out, target, M)
+        if weighted:
+            dyb, loss_part = loss_head(out, target, M, loss_name,
+                                       sample_weight, pos_weight)
+        else:
+            dyb, loss_part = bce_head(out, target, M)
     else:
         a1t, mask1, a2t, mask2, a3, out, dyb, loss_part = (
             hip.fwd_chain_bf16(
                 x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"],
                 b4, target=target, xt_out=xt, pi16=_PI16, **_rows_kw(),
                 **_loss_kw(loss_code),
+                **_weight_kw(
+                    None if sample_weight is None
+                    else sample_weight.to(x.device),
+                    pos_weight),
             )
         )
     loss = loss_part.sum() / M

@@ -13,6 +13,11 @@ label_column/shape/type with identical defaults and normalization), yields
   * ``feature_matrix=True`` (MI355X extension): when the engine produced a
     fused feature matrix column, yields ``([features_matrix], labels)`` with
     zero per-batch work — the flagship benchmark path.
+  * ``weight_column`` (MI355X extension): a per-row sample-weight column
+    travels through the shuffle like the label and batches become
+    ``(features, label, weight)`` with ``weight`` shaped ``[B]`` — never
+    standardized and never fused into the feature matrix, for
+    ``fused_step(sample_weight=)`` / ``FusedEvaluator(weighted=True)``.
 """
 
 import functools
@@ -49,10 +54,31 @@ class TorchShufflingDataset(IterableDataset):
         label_type: Optional[torch.dtype] = None,
         feature_matrix: bool = False,
         normalize_features: bool = False,
+        weight_column: Any = None,
+        weight_type: torch.dtype = torch.float,
         **engine_kwargs,
     ):
         super().__init__()
         self._feature_matrix = feature_matrix
+        caller_out_dtypes = "out_dtypes" in engine_kwargs
+        if weight_column is not None:
+            names = (
+                list(feature_columns)
+                if isinstance(feature_columns, list)
+                else [feature_columns]
+            )
+            if weight_column in names:
+                raise ValueError(
+                    f"weight_column {weight_column!r} is also listed in "
+                    "feature_columns: a sample weight is not a feature"
+                )
+            # The weight's dtype comes out of the fused unpack kernel (an
+            # fp64 source column needs no per-batch cast) unless the caller
+            # already chose one. It is in none of the default normalize=
+            # lists below and is no member of the feature matrix.
+            out_dtypes = dict(engine_kwargs.get("out_dtypes") or {})
+            out_dtypes.setdefault(weight_column, weight_type)
+            engine_kwargs["out_dtypes"] = out_dtypes
         if normalize_features and not feature_matrix:
             names = (
                 list(feature_columns)
@@ -85,9 +111,11 @@ class TorchShufflingDataset(IterableDataset):
             if feature_types and isinstance(feature_types, list):
                 ft = feature_types[0]
                 if isinstance(ft, torch.dtype) and ft != torch.float32:
-                    engine_kwargs.setdefault(
-                        "out_dtypes", {"__features__": ft}
-                    )
+                    if not caller_out_dtypes:
+                        # (with a weight_column, beside its entry)
+                        engine_kwargs.setdefault("out_dtypes", {})[
+                            "__features__"
+                        ] = ft
             if normalize_features:
                 engine_kwargs.setdefault(
                     "normalize", [engine_kwargs["feature_matrix"][0]]
@@ -111,6 +139,8 @@ class TorchShufflingDataset(IterableDataset):
             label_shape=label_shape,
             label_type=label_type,
             feature_matrix=feature_matrix,
+            weight_column=weight_column,
+            weight_type=weight_type,
         )
 
     def set_epoch(self, epoch):
@@ -188,9 +218,12 @@ def rowblock_to_tensor_factory(
     label_shape: Optional[int] = None,
     label_type: Optional[torch.dtype] = None,
     feature_matrix: bool = False,
+    weight_column: Any = None,
+    weight_type: torch.dtype = torch.float,
 ) -> Callable[[RowBlock], Tuple[List[torch.Tensor], torch.Tensor]]:
     """RowBlock -> (List[Tensor], Tensor) converter (the reference's
-    dataframe_to_tensor_factory, torch_dataset.py:95-141)."""
+    dataframe_to_tensor_factory, torch_dataset.py:95-141); with
+    ``weight_column`` -> (List[Tensor], Tensor, Tensor)."""
     (
         feature_columns,
         feature_shapes,
@@ -215,6 +248,8 @@ def rowblock_to_tensor_factory(
         label_shape=label_shape,
         label_type=label_type,
         feature_matrix=feature_matrix,
+        weight_column=weight_column,
+        weight_type=weight_type,
     )
 
 
@@ -250,10 +285,22 @@ def convert_to_tensor(
     label_shape: Optional[int],
     label_type: torch.dtype,
     feature_matrix: bool = False,
+    weight_column: Any = None,
+    weight_type: torch.dtype = torch.float,
 ) -> Tuple[List[torch.Tensor], torch.Tensor]:
     """Per-batch conversion (reference torch_dataset.py:204-236). On the
     MI355X path the heavy cast/pack already happened in the fused reducer
-    kernel, so this is views + dtype adjustments only."""
+    kernel, so this is views + dtype adjustments only. With
+    ``weight_column`` the result is a 3-tuple whose last member is the
+    ``[B]`` sample weight."""
+    if weight_column is not None:
+        feats, label = convert_to_tensor(
+            block, feature_columns, feature_shapes, feature_types,
+            label_column, label_shape, label_type, feature_matrix,
+        )
+        # ``.to`` is a no-op when the engine already produced weight_type
+        weight = _col_tensor(block, weight_column).to(weight_type)
+        return feats, label, weight.reshape(-1)
     if feature_matrix and isinstance(block, RowBlock) and (
         "__features__" in block.columns
     ):
