@@ -3,8 +3,9 @@ evaluator, same process, same build (models/fused_step.py,
 models/fused_eval.py), at the bench shape.
 
 Step arms, all ``fused_step(loss="bce")`` on the same batch and model:
-  bce             unweighted (fwd_chain_kernel, what the step always ran)
-  bce_w           ``sample_weight=w`` (fwd_chain_w_kernel)
+  bce             unweighted (fwd_chain_kernel, WEIGHTED = false: what the
+                  step always ran)
+  bce_w           ``sample_weight=w`` (fwd_chain_kernel, WEIGHTED = true)
   bce_w_pw        ``sample_weight=w, pos_weight=3`` (the pos_weight branch)
 Evaluator arms, ``FusedEvaluator(task="binary").update`` on a model whose
 logits are spread like a trained one's (std ~2):

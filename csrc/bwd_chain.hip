@@ -43,6 +43,8 @@
 
 #include <cstdint>
 
+#include "chain.h"
+
 namespace rsdl {
 
 // A/B'd: nontemporal streaming accesses measure ~4% faster than
@@ -456,29 +458,26 @@ int64_t bwd_chain_grid(int64_t M, int rows) {
   return (M + rows - 1) / rows;
 }
 
-void launch_bwd_chain(const void* dy, const void* a3, const void* mask1,
-                      const void* mask2, const void* w4, const void* W3T,
-                      const void* W2T, void* dz1t, void* dz2t, void* dz3t,
-                      float* db_part, int64_t M, int pi16, int rows,
-                      hipStream_t stream) {
-  const int32_t grid = (int32_t)bwd_chain_grid(M, rows);
+void launch_bwd_chain(const BwdChainArgs& p, hipStream_t stream) {
+  const int32_t grid = (int32_t)bwd_chain_grid(p.M, p.rows);
   // The global layouts are per 32-row m-tile whatever the slab size.
-  const int64_t mchunks = (M + BC_MT - 1) / BC_MT * 2;
-  auto kern = rows == 64
-      ? (pi16 ? bwd_chain_kernel<2, true> : bwd_chain_kernel<2, false>)
-      : (pi16 ? bwd_chain_kernel<1, true> : bwd_chain_kernel<1, false>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+  const int64_t mchunks = (p.M + BC_MT - 1) / BC_MT * 2;
+  auto kern = p.rows == 64
+      ? (p.pi16 ? bwd_chain_kernel<2, true> : bwd_chain_kernel<2, false>)
+      : (p.pi16 ? bwd_chain_kernel<1, true> : bwd_chain_kernel<1, false>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(p.rows == 64 ? 512 : 256), 0,
                      stream,
-                     reinterpret_cast<const short*>(dy),
-                     reinterpret_cast<const short*>(a3),
-                     reinterpret_cast<const uint32_t*>(mask1),
-                     reinterpret_cast<const uint32_t*>(mask2),
-                     reinterpret_cast<const short*>(w4),
-                     reinterpret_cast<const short*>(W3T),
-                     reinterpret_cast<const short*>(W2T),
-                     reinterpret_cast<short*>(dz1t),
-                     reinterpret_cast<short*>(dz2t),
-                     reinterpret_cast<short*>(dz3t), db_part, M, mchunks);
+                     reinterpret_cast<const short*>(p.dy),
+                     reinterpret_cast<const short*>(p.a3),
+                     reinterpret_cast<const uint32_t*>(p.mask1),
+                     reinterpret_cast<const uint32_t*>(p.mask2),
+                     reinterpret_cast<const short*>(p.w4),
+                     reinterpret_cast<const short*>(p.W3T),
+                     reinterpret_cast<const short*>(p.W2T),
+                     reinterpret_cast<short*>(p.dz1t),
+                     reinterpret_cast<short*>(p.dz2t),
+                     reinterpret_cast<short*>(p.dz3t), p.db_part, p.M,
+                     mchunks);
 }
 
 }  // namespace rsdl

@@ -69,6 +69,8 @@
 
 #include <cstdint>
 
+#include "chain.h"
+
 namespace rsdl {
 
 // A/B'd: nontemporal streaming accesses measure ~4% faster than
@@ -414,8 +416,8 @@ __device__ __forceinline__ int32_t fc_fresh_lane(int32_t lane) {
 // LOSS picks the head epilogue only (FC_LOSS_MSE: dyb = 2/M (o-t), terms
 // (o-t)^2; FC_LOSS_BCE: dyb = 1/M (sigmoid(o)-t), terms from
 // fc_bce_terms); the layers, the LDS plan and the barriers do not see it.
-// WEIGHTED (the fwd_chain_w_kernel entry points; the unweighted ones
-// pass false and compile to what they did before the flag existed): the
+// WEIGHTED (fwd_chain_kernel<.., true>; the false instantiations read
+// neither argument and compile to what they did before the flag existed): the
 // head also takes ``weight`` (fp32 [M], read under the m0 + m < M guard
 // only; null = every w is 1) and ``pos_weight`` p, normalisation still by
 // M. MSE: dyb = bf16((2/M w)(o-t)), terms w (o-t)^2. BCE, p == 1: dyb =
@@ -567,7 +569,9 @@ __device__ __forceinline__ void fc_fwd_chain_body(
   fc_store_tile<MT, FC_N3, FC_S3>(t3, a3, m0, M, tid);
 }
 
-template <int MT, bool PI16, int LOSS = FC_LOSS_MSE>
+// The one entry point per instantiation. ``weight`` and ``pos_weight`` are
+// always in the argument list; the WEIGHTED = false body never reads them.
+template <int MT, bool PI16, int LOSS, bool WEIGHTED>
 __global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
 fwd_chain_kernel(
     const short* __restrict__ x0s, const short* __restrict__ W1,
@@ -579,29 +583,9 @@ fwd_chain_kernel(
     uint32_t* __restrict__ mask2, short* __restrict__ a3,
     short* __restrict__ out, const float* __restrict__ target,
     short* __restrict__ dyb, float* __restrict__ loss_part, float inv_m,
-    int64_t M, int64_t mchunks) {
-  fc_fwd_chain_body<MT, PI16, LOSS, false>(
-      x0s, W1, b1, W2, b2, W3, b3, w4, b4, a1t, mask1, a2t, mask2, a3, out,
-      target, dyb, loss_part, inv_m, M, mchunks, nullptr, 1.f);
-}
-
-// The weighted head (sample weights and/or pos_weight); launched only when
-// the caller passes either, so the default step runs fwd_chain_kernel.
-template <int MT, bool PI16, int LOSS>
-__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
-fwd_chain_w_kernel(
-    const short* __restrict__ x0s, const short* __restrict__ W1,
-    const float* __restrict__ b1, const short* __restrict__ W2,
-    const float* __restrict__ b2, const short* __restrict__ W3,
-    const float* __restrict__ b3, const short* __restrict__ w4,
-    const float* __restrict__ b4, short* __restrict__ a1t,
-    uint32_t* __restrict__ mask1, short* __restrict__ a2t,
-    uint32_t* __restrict__ mask2, short* __restrict__ a3,
-    short* __restrict__ out, const float* __restrict__ target,
-    short* __restrict__ dyb, float* __restrict__ loss_part, float inv_m,
     int64_t M, int64_t mchunks, const float* __restrict__ weight,
     float pos_weight) {
-  fc_fwd_chain_body<MT, PI16, LOSS, true>(
+  fc_fwd_chain_body<MT, PI16, LOSS, WEIGHTED>(
       x0s, W1, b1, W2, b2, W3, b3, w4, b4, a1t, mask1, a2t, mask2, a3, out,
       target, dyb, loss_part, inv_m, M, mchunks, weight, pos_weight);
 }
@@ -630,8 +614,8 @@ fwd_chain_w_kernel(
 // kept): the streaming-AUC histogram. Integer atomics commute, so the
 // histogram does not depend on launch or arrival order. A NaN logit lands
 // wherever its bits put it. ``hist`` is ignored by the regression task.
-// WEIGHTED (the eval_chain_w_kernel entry points; the unweighted ones
-// compile to what they did before the flag existed): ``weight`` (fp32 [M],
+// WEIGHTED (eval_chain_kernel<.., true>; the false instantiations never
+// read ``weight`` and compile to what they did): ``weight`` (fp32 [M],
 // read under the m0 + m < M guard only; null = every w is 1) scales every
 // term and a fifth partial carries the weight sum, in rows of EIGHT floats
 // (two aligned float4 for eval_accumulate; columns 5-7 are written as 0):
@@ -777,7 +761,7 @@ __device__ __forceinline__ void fc_eval_chain_body(
   }
 }
 
-template <int MT, int TASK = FC_LOSS_MSE>
+template <int MT, int TASK, bool WEIGHTED>
 __global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
 eval_chain_kernel(
     const short* __restrict__ x0s, const short* __restrict__ W1,
@@ -786,26 +770,11 @@ eval_chain_kernel(
     const float* __restrict__ b3, const short* __restrict__ w4,
     const float* __restrict__ b4, float* __restrict__ pred,
     const float* __restrict__ target, float* __restrict__ part, int64_t M,
-    int64_t mchunks, unsigned long long* __restrict__ hist) {
-  fc_eval_chain_body<MT, TASK, false>(x0s, W1, b1, W2, b2, W3, b3, w4, b4,
-                                      pred, target, part, M, mchunks, hist,
-                                      nullptr);
-}
-
-template <int MT, int TASK>
-__global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
-eval_chain_w_kernel(
-    const short* __restrict__ x0s, const short* __restrict__ W1,
-    const float* __restrict__ b1, const short* __restrict__ W2,
-    const float* __restrict__ b2, const short* __restrict__ W3,
-    const float* __restrict__ b3, const short* __restrict__ w4,
-    const float* __restrict__ b4, float* __restrict__ pred,
-    const float* __restrict__ target, float* __restrict__ part, int64_t M,
     int64_t mchunks, unsigned long long* __restrict__ hist,
     const float* __restrict__ weight) {
-  fc_eval_chain_body<MT, TASK, true>(x0s, W1, b1, W2, b2, W3, b3, w4, b4,
-                                     pred, target, part, M, mchunks, hist,
-                                     weight);
+  fc_eval_chain_body<MT, TASK, WEIGHTED>(x0s, W1, b1, W2, b2, W3, b3, w4, b4,
+                                         pred, target, part, M, mchunks,
+                                         hist, weight);
 }
 
 // x [M,100] bf16 -> fragment-major [ceil(M/32)][7][2][32][8] with zero
@@ -994,137 +963,75 @@ int64_t fwd_chain_grid(int64_t M, int rows) {
   return (M + rows - 1) / rows;
 }
 
-void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
-                      const void* W2, const float* b2, const void* W3,
-                      const float* b3, const void* w4, const float* b4,
-                      void* a1t, uint32_t* mask1, void* a2t,
-                      uint32_t* mask2, void* a3, void* out,
-                      const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, int rows, int loss,
-                      hipStream_t stream) {
-  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
+// The instantiation of a (rows, pi16, loss, weighted) call, picked in one
+// place per family. The weighted instantiations run only when the binding
+// asks for them (a weight tensor or a pos_weight != 1, with a target), so
+// the default step and the default evaluator launch the unweighted ones.
+template <int MT, bool PI16, int LOSS>
+static auto fwd_chain_pick(bool weighted) {
+  return weighted ? fwd_chain_kernel<MT, PI16, LOSS, true>
+                  : fwd_chain_kernel<MT, PI16, LOSS, false>;
+}
+template <int MT, bool PI16>
+static auto fwd_chain_pick(int loss, bool weighted) {
+  return loss == FC_LOSS_BCE ? fwd_chain_pick<MT, PI16, FC_LOSS_BCE>(weighted)
+                             : fwd_chain_pick<MT, PI16, FC_LOSS_MSE>(weighted);
+}
+template <int MT>
+static auto fwd_chain_pick(int pi16, int loss, bool weighted) {
+  return pi16 ? fwd_chain_pick<MT, true>(loss, weighted)
+              : fwd_chain_pick<MT, false>(loss, weighted);
+}
+
+void launch_fwd_chain(const FwdChainArgs& p, hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(p.M, p.rows);
   // The global layouts are per 32-row m-tile whatever the slab size.
-  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
-  auto kern = rows == 64
-      ? (pi16 ? fwd_chain_kernel<2, true> : fwd_chain_kernel<2, false>)
-      : (pi16 ? fwd_chain_kernel<1, true> : fwd_chain_kernel<1, false>);
-  if (loss == FC_LOSS_BCE) {
-    kern = rows == 64
-        ? (pi16 ? fwd_chain_kernel<2, true, FC_LOSS_BCE>
-                : fwd_chain_kernel<2, false, FC_LOSS_BCE>)
-        : (pi16 ? fwd_chain_kernel<1, true, FC_LOSS_BCE>
-                : fwd_chain_kernel<1, false, FC_LOSS_BCE>);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+  const int64_t mchunks = (p.M + FC_MT - 1) / FC_MT * 2;
+  auto kern = p.rows == 64 ? fwd_chain_pick<2>(p.pi16, p.loss, p.weighted)
+                           : fwd_chain_pick<1>(p.pi16, p.loss, p.weighted);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(p.rows == 64 ? 512 : 256), 0,
                      stream,
-                     reinterpret_cast<const short*>(x0s),
-                     reinterpret_cast<const short*>(W1), b1,
-                     reinterpret_cast<const short*>(W2), b2,
-                     reinterpret_cast<const short*>(W3), b3,
-                     reinterpret_cast<const short*>(w4), b4,
-                     reinterpret_cast<short*>(a1t), mask1,
-                     reinterpret_cast<short*>(a2t), mask2,
-                     reinterpret_cast<short*>(a3),
-                     reinterpret_cast<short*>(out), target,
-                     reinterpret_cast<short*>(dyb), loss_part,
-                     target ? 1.f / (float)M : 0.f, M, mchunks);
+                     reinterpret_cast<const short*>(p.x0s),
+                     reinterpret_cast<const short*>(p.w.W1), p.w.b1,
+                     reinterpret_cast<const short*>(p.w.W2), p.w.b2,
+                     reinterpret_cast<const short*>(p.w.W3), p.w.b3,
+                     reinterpret_cast<const short*>(p.w.w4), p.w.b4,
+                     reinterpret_cast<short*>(p.a1t), p.mask1,
+                     reinterpret_cast<short*>(p.a2t), p.mask2,
+                     reinterpret_cast<short*>(p.a3),
+                     reinterpret_cast<short*>(p.out), p.target,
+                     reinterpret_cast<short*>(p.dyb), p.loss_part,
+                     p.target ? 1.f / (float)p.M : 0.f, p.M, mchunks,
+                     p.weight, p.pos_weight);
 }
 
-// The weighted head: ``weight`` fp32 [M] or null (every w = 1),
-// ``pos_weight`` > 0 (BCE only; the binding rejects it for MSE). ``target``
-// must not be null. The binding comes here only when a weight or a
-// pos_weight != 1 was given.
-void launch_fwd_chain_w(const void* x0s, const void* W1, const float* b1,
-                        const void* W2, const float* b2, const void* W3,
-                        const float* b3, const void* w4, const float* b4,
-                        void* a1t, uint32_t* mask1, void* a2t,
-                        uint32_t* mask2, void* a3, void* out,
-                        const float* target, void* dyb, float* loss_part,
-                        int64_t M, int pi16, int rows, int loss,
-                        const float* weight, float pos_weight,
-                        hipStream_t stream) {
-  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
-  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
-  auto kern = rows == 64
-      ? (pi16 ? fwd_chain_w_kernel<2, true, FC_LOSS_MSE>
-              : fwd_chain_w_kernel<2, false, FC_LOSS_MSE>)
-      : (pi16 ? fwd_chain_w_kernel<1, true, FC_LOSS_MSE>
-              : fwd_chain_w_kernel<1, false, FC_LOSS_MSE>);
-  if (loss == FC_LOSS_BCE) {
-    kern = rows == 64
-        ? (pi16 ? fwd_chain_w_kernel<2, true, FC_LOSS_BCE>
-                : fwd_chain_w_kernel<2, false, FC_LOSS_BCE>)
-        : (pi16 ? fwd_chain_w_kernel<1, true, FC_LOSS_BCE>
-                : fwd_chain_w_kernel<1, false, FC_LOSS_BCE>);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
-                     stream,
-                     reinterpret_cast<const short*>(x0s),
-                     reinterpret_cast<const short*>(W1), b1,
-                     reinterpret_cast<const short*>(W2), b2,
-                     reinterpret_cast<const short*>(W3), b3,
-                     reinterpret_cast<const short*>(w4), b4,
-                     reinterpret_cast<short*>(a1t), mask1,
-                     reinterpret_cast<short*>(a2t), mask2,
-                     reinterpret_cast<short*>(a3),
-                     reinterpret_cast<short*>(out), target,
-                     reinterpret_cast<short*>(dyb), loss_part,
-                     1.f / (float)M, M, mchunks, weight, pos_weight);
+template <int MT, int TASK>
+static auto eval_chain_pick(bool weighted) {
+  return weighted ? eval_chain_kernel<MT, TASK, true>
+                  : eval_chain_kernel<MT, TASK, false>;
+}
+template <int MT>
+static auto eval_chain_pick(int task, bool weighted) {
+  return task == FC_LOSS_BCE ? eval_chain_pick<MT, FC_LOSS_BCE>(weighted)
+                             : eval_chain_pick<MT, FC_LOSS_MSE>(weighted);
 }
 
-// Forward-only evaluation chain: ``pred`` (fp32 [M]) and/or ``target``
-// with ``part`` (fp32 [fwd_chain_grid(M, rows), 4]); either may be null.
-// ``task`` = FC_LOSS_MSE (regression partials) or FC_LOSS_BCE (binary
-// partials, plus the AUC histogram when ``hist`` is not null).
-void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
-                       const void* W2, const float* b2, const void* W3,
-                       const float* b3, const void* w4, const float* b4,
-                       float* pred, const float* target, float* part,
-                       int64_t M, int rows, int task, int64_t* hist,
-                       hipStream_t stream) {
-  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
-  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
-  auto kern = rows == 64 ? eval_chain_kernel<2> : eval_chain_kernel<1>;
-  if (task == FC_LOSS_BCE) {
-    kern = rows == 64 ? eval_chain_kernel<2, FC_LOSS_BCE>
-                      : eval_chain_kernel<1, FC_LOSS_BCE>;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
+// Forward-only evaluation chain (EvalChainArgs in chain.h).
+void launch_eval_chain(const EvalChainArgs& p, hipStream_t stream) {
+  const int32_t grid = (int32_t)fwd_chain_grid(p.M, p.rows);
+  const int64_t mchunks = (p.M + FC_MT - 1) / FC_MT * 2;
+  auto kern = p.rows == 64 ? eval_chain_pick<2>(p.task, p.weighted)
+                           : eval_chain_pick<1>(p.task, p.weighted);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(p.rows == 64 ? 512 : 256), 0,
                      stream,
-                     reinterpret_cast<const short*>(x0s),
-                     reinterpret_cast<const short*>(W1), b1,
-                     reinterpret_cast<const short*>(W2), b2,
-                     reinterpret_cast<const short*>(W3), b3,
-                     reinterpret_cast<const short*>(w4), b4, pred, target,
-                     part, M, mchunks,
-                     reinterpret_cast<unsigned long long*>(hist));
-}
-
-// Weighted evaluation chain: ``target`` and ``part`` (fp32 [grid, 8]) are
-// required, ``weight`` fp32 [M] or null (every w = 1).
-void launch_eval_chain_w(const void* x0s, const void* W1, const float* b1,
-                         const void* W2, const float* b2, const void* W3,
-                         const float* b3, const void* w4, const float* b4,
-                         float* pred, const float* target, float* part,
-                         int64_t M, int rows, int task, int64_t* hist,
-                         const float* weight, hipStream_t stream) {
-  const int32_t grid = (int32_t)fwd_chain_grid(M, rows);
-  const int64_t mchunks = (M + FC_MT - 1) / FC_MT * 2;
-  auto kern = rows == 64 ? eval_chain_w_kernel<2, FC_LOSS_MSE>
-                         : eval_chain_w_kernel<1, FC_LOSS_MSE>;
-  if (task == FC_LOSS_BCE) {
-    kern = rows == 64 ? eval_chain_w_kernel<2, FC_LOSS_BCE>
-                      : eval_chain_w_kernel<1, FC_LOSS_BCE>;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(rows == 64 ? 512 : 256), 0,
-                     stream,
-                     reinterpret_cast<const short*>(x0s),
-                     reinterpret_cast<const short*>(W1), b1,
-                     reinterpret_cast<const short*>(W2), b2,
-                     reinterpret_cast<const short*>(W3), b3,
-                     reinterpret_cast<const short*>(w4), b4, pred, target,
-                     part, M, mchunks,
-                     reinterpret_cast<unsigned long long*>(hist), weight);
+                     reinterpret_cast<const short*>(p.x0s),
+                     reinterpret_cast<const short*>(p.w.W1), p.w.b1,
+                     reinterpret_cast<const short*>(p.w.W2), p.w.b2,
+                     reinterpret_cast<const short*>(p.w.W3), p.w.b3,
+                     reinterpret_cast<const short*>(p.w.w4), p.w.b4, p.pred,
+                     p.target, p.part, p.M, mchunks,
+                     reinterpret_cast<unsigned long long*>(p.hist),
+                     p.weight);
 }
 
 }  // namespace rsdl

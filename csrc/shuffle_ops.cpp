@@ -17,6 +17,7 @@
 #include <tuple>
 #include <vector>
 
+#include "chain.h"
 #include "step_glue.h"
 
 namespace rsdl {
@@ -101,55 +102,6 @@ void launch_wgrad_wide(const void* dy, const void* x, float* dW, float* db,
 void launch_relu_bwd_bias(const void* dy, const void* y, void* dx,
                           float* db_part, int64_t nvec, int32_t N,
                           int32_t grid, hipStream_t stream);
-int64_t fwd_chain_grid(int64_t M, int rows);
-void launch_swizzle_x(const void* x, void* out, int64_t M,
-                      hipStream_t stream);
-void launch_swizzle_xt(const void* x, void* out, int64_t M, int pi16,
-                       hipStream_t stream);
-void launch_swizzle_x_both(const void* x, void* xs, void* xt, int64_t M,
-                           int pi16, hipStream_t stream);
-void launch_fwd_chain(const void* x0s, const void* W1, const float* b1,
-                      const void* W2, const float* b2, const void* W3,
-                      const float* b3, const void* w4, const float* b4,
-                      void* a1t, uint32_t* mask1, void* a2t,
-                      uint32_t* mask2, void* a3, void* out,
-                      const float* target, void* dyb, float* loss_part,
-                      int64_t M, int pi16, int rows, int loss,
-                      hipStream_t stream);
-void launch_eval_chain(const void* x0s, const void* W1, const float* b1,
-                       const void* W2, const float* b2, const void* W3,
-                       const float* b3, const void* w4, const float* b4,
-                       float* pred, const float* target, float* part,
-                       int64_t M, int rows, int task, int64_t* hist,
-                       hipStream_t stream);
-void launch_fwd_chain_w(const void* x0s, const void* W1, const float* b1,
-                        const void* W2, const float* b2, const void* W3,
-                        const float* b3, const void* w4, const float* b4,
-                        void* a1t, uint32_t* mask1, void* a2t,
-                        uint32_t* mask2, void* a3, void* out,
-                        const float* target, void* dyb, float* loss_part,
-                        int64_t M, int pi16, int rows, int loss,
-                        const float* weight, float pos_weight,
-                        hipStream_t stream);
-void launch_eval_chain_w(const void* x0s, const void* W1, const float* b1,
-                         const void* W2, const float* b2, const void* W3,
-                         const float* b3, const void* w4, const float* b4,
-                         float* pred, const float* target, float* part,
-                         int64_t M, int rows, int task, int64_t* hist,
-                         const float* weight, hipStream_t stream);
-int64_t bwd_chain_grid(int64_t M, int rows);
-void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
-                       int32_t K, int64_t mchunks, int32_t nt_w,
-                       int32_t kt_w, hipStream_t stream);
-int64_t wgrad_frag_nslabs(int64_t mchunks, int32_t N, int32_t K,
-                          int32_t nt_w, int32_t kt_w);
-void launch_slab_reduce(const float* part, float* out, int64_t nk,
-                        int64_t nslabs, hipStream_t stream);
-void launch_bwd_chain(const void* dy, const void* a3, const void* mask1,
-                      const void* mask2, const void* w4, const void* W3T,
-                      const void* W2T, void* dz1t, void* dz2t, void* dz3t,
-                      float* db_part, int64_t M, int pi16, int rows,
-                      hipStream_t stream);
 
 namespace {
 
@@ -710,6 +662,29 @@ static int chain_loss(int64_t loss, const char* who, const char* what) {
   return static_cast<int>(loss);
 }
 
+// The feature batch every chain binding takes.
+static void check_x(const char* who, const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
+              who, ": x must be contiguous bf16 [M,100]");
+}
+
+// fp32 ``biases`` [b1..b4] read in place; with ``on`` (x's device index)
+// they must also sit on that GPU.
+static void check_biases(const char* who,
+                         const std::vector<at::Tensor>& biases, int on = -1) {
+  TORCH_CHECK(biases.size() == 4, who, ": biases must be [b1..b4]");
+  const int64_t bn[4] = {512, 256, 128, 1};
+  for (int i = 0; i < 4; i++) {
+    TORCH_CHECK(biases[i].is_cuda() &&
+                    biases[i].scalar_type() == at::kFloat &&
+                    biases[i].is_contiguous() && biases[i].numel() == bn[i] &&
+                    (on < 0 || biases[i].get_device() == on),
+                who, ": bias ", i, " must be contiguous fp32 [", bn[i],
+                on < 0 ? "] on GPU" : "] on x's GPU");
+  }
+}
+
 // Sample weights and pos_weight of the fused head (csrc/fwd_chain.hip),
 // validated for ``who``: ``weight`` fp32 [M] on x's GPU or absent (every
 // w = 1), ``pos_weight`` finite and > 0, and != 1 only with LOSS_BCE.
@@ -773,16 +748,14 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
   f.mask2 = at::empty({mtiles, 256}, x.options().dtype(at::kInt));
   f.a3 = at::empty({M, 128}, x.options());
   f.out = at::empty({M, 1}, x.options());
-  const float* tgt_ptr = nullptr;
-  void* dyb_ptr = nullptr;
-  float* lp_ptr = nullptr;
+  FwdChainArgs p{};
   if (tgt != nullptr) {
     f.dyb = at::empty({M, 1}, x.options());
     f.loss_part = at::empty({std::max<int64_t>(fwd_chain_grid(M, rows), 1)},
                             x.options().dtype(at::kFloat));
-    tgt_ptr = tgt->data_ptr<float>();
-    dyb_ptr = f.dyb.data_ptr();
-    lp_ptr = f.loss_part.data_ptr<float>();
+    p.target = tgt->data_ptr<float>();
+    p.dyb = f.dyb.data_ptr();
+    p.loss_part = f.loss_part.data_ptr<float>();
   }
   if (M > 0) {
     // x pre-swizzled to the same fragment-major layout (per 32-row
@@ -801,30 +774,25 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
     } else {
       launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
     }
-    if (hw.on && tgt_ptr != nullptr) {
-      launch_fwd_chain_w(
-          xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
-          W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
-          b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
-          f.a1t.data_ptr(),
-          reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
-          f.a2t.data_ptr(),
-          reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
-          f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
-          pi16 ? 1 : 0, rows, loss, hw.weight, hw.pos_weight,
-          current_stream());
-    } else {
-      launch_fwd_chain(
-          xs.data_ptr(), W1s.data_ptr(), b1f.data_ptr<float>(),
-          W2s.data_ptr(), b2f.data_ptr<float>(), W3s.data_ptr(),
-          b3f.data_ptr<float>(), w4.data_ptr(), b4f.data_ptr<float>(),
-          f.a1t.data_ptr(),
-          reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>()),
-          f.a2t.data_ptr(),
-          reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>()),
-          f.a3.data_ptr(), f.out.data_ptr(), tgt_ptr, dyb_ptr, lp_ptr, M,
-          pi16 ? 1 : 0, rows, loss, current_stream());
-    }
+    p.x0s = xs.data_ptr();
+    p.w = {W1s.data_ptr(), b1f.data_ptr<float>(), W2s.data_ptr(),
+           b2f.data_ptr<float>(), W3s.data_ptr(), b3f.data_ptr<float>(),
+           w4.data_ptr(), b4f.data_ptr<float>()};
+    p.a1t = f.a1t.data_ptr();
+    p.mask1 = reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>());
+    p.a2t = f.a2t.data_ptr();
+    p.mask2 = reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>());
+    p.a3 = f.a3.data_ptr();
+    p.out = f.out.data_ptr();
+    p.M = M;
+    p.pi16 = pi16 ? 1 : 0;
+    p.rows = rows;
+    p.loss = loss;
+    // the weighted head has nothing to weigh without a target
+    p.weighted = hw.on && tgt != nullptr;
+    p.weight = hw.weight;
+    p.pos_weight = hw.pos_weight;
+    launch_fwd_chain(p, current_stream());
   }
   return f;
 }
@@ -844,9 +812,7 @@ std::vector<at::Tensor> fwd_chain_bf16(
       head_weights("fwd_chain", x, weight, pos_weight, closs);
   TORCH_CHECK(!hw.on || target.has_value(),
               "fwd_chain: weight / pos_weight need a target");
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
-              "fwd_chain: x must be contiguous bf16 [M,100]");
+  check_x("fwd_chain", x);
   auto chk_w = [](const at::Tensor& W, int64_t n, int64_t k,
                   const char* nm) {
     TORCH_CHECK(W.is_cuda() && W.scalar_type() == at::kBFloat16 &&
@@ -944,11 +910,22 @@ BwdChainOut run_bwd_chain(const at::Tensor& dy, const at::Tensor& a3,
                         dy.options().dtype(at::kFloat));
   if (M == 0) b.db_part.zero_();
   if (M > 0) {
-    launch_bwd_chain(dy.data_ptr(), a3.data_ptr(), mask1.data_ptr(),
-                     mask2.data_ptr(), w4c.data_ptr(), W3Ts.data_ptr(),
-                     W2Ts.data_ptr(), b.dz1t.data_ptr(), b.dz2t.data_ptr(),
-                     b.dz3t.data_ptr(), b.db_part.data_ptr<float>(), M,
-                     pi16 ? 1 : 0, rows, current_stream());
+    BwdChainArgs p{};
+    p.dy = dy.data_ptr();
+    p.a3 = a3.data_ptr();
+    p.mask1 = mask1.data_ptr();
+    p.mask2 = mask2.data_ptr();
+    p.w4 = w4c.data_ptr();
+    p.W3T = W3Ts.data_ptr();
+    p.W2T = W2Ts.data_ptr();
+    p.dz1t = b.dz1t.data_ptr();
+    p.dz2t = b.dz2t.data_ptr();
+    p.dz3t = b.dz3t.data_ptr();
+    p.db_part = b.db_part.data_ptr<float>();
+    p.M = M;
+    p.pi16 = pi16 ? 1 : 0;
+    p.rows = rows;
+    launch_bwd_chain(p, current_stream());
   }
   return b;
 }
@@ -1040,9 +1017,7 @@ at::Tensor run_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT,
 // x [M,100] -> wgrad fragment-major x^T ([128/32][mchunks][2][32][8],
 // zero-padded cols 100..127 and rows past M) for the dW1 wgrad.
 at::Tensor swizzle_xt_bf16(const at::Tensor& x, bool pi16) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
-              "swizzle_xt: x must be contiguous bf16 [M,100]");
+  check_x("swizzle_xt", x);
   const int64_t M = x.size(0);
   const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
   auto out = at::empty({4 * mtiles * 2 * 512}, x.options());
@@ -1279,21 +1254,11 @@ std::vector<at::Tensor> fused_step_bf16(
   const int closs = chain_loss(loss, "fused_step", "loss");
   const HeadWeights hw =
       head_weights("fused_step", x, weight, pos_weight, closs);
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
-              "fused_step: x must be contiguous bf16 [M,100]");
+  check_x("fused_step", x);
   const int64_t M = x.size(0);
   TORCH_CHECK(M > 0, "fused_step: empty batch");
   TORCH_CHECK(target.numel() == M, "fused_step: target size mismatch");
-  TORCH_CHECK(biases.size() == 4, "fused_step: biases must be [b1..b4]");
-  const int64_t bn[4] = {512, 256, 128, 1};
-  for (int i = 0; i < 4; i++) {
-    TORCH_CHECK(biases[i].is_cuda() &&
-                    biases[i].scalar_type() == at::kFloat &&
-                    biases[i].is_contiguous() && biases[i].numel() == bn[i],
-                "fused_step: bias ", i, " must be contiguous fp32 [", bn[i],
-                "] on GPU");
-  }
+  check_biases("fused_step", biases);
   auto pr = run_step_prep(weights, target, c10::nullopt);
   const int64_t mchunks = 2 * ((M + 31) / 32);
   c10::optional<at::Tensor> xt =
@@ -1343,9 +1308,7 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
                 const c10::optional<at::Tensor>& weight) {
   const int crows = chain_rows(rows);
   const int ctask = chain_loss(task, "eval_chain", "task");
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
-                  x.dim() == 2 && x.size(1) == 100 && x.is_contiguous(),
-              "eval_chain: x must be contiguous bf16 [M,100]");
+  check_x("eval_chain", x);
   const int64_t M = x.size(0);
   TORCH_CHECK(Wstage.size() == 4,
               "eval_chain: Wstage must be [W1s, W2s, W3s, w4b]");
@@ -1361,16 +1324,7 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
                 " must be contiguous aligned bf16 with ", wn[i],
                 " elements on x's GPU");
   }
-  TORCH_CHECK(biases.size() == 4, "eval_chain: biases must be [b1..b4]");
-  const int64_t bn[4] = {512, 256, 128, 1};
-  for (int i = 0; i < 4; i++) {
-    TORCH_CHECK(biases[i].is_cuda() &&
-                    biases[i].scalar_type() == at::kFloat &&
-                    biases[i].is_contiguous() && biases[i].numel() == bn[i] &&
-                    biases[i].get_device() == x.get_device(),
-                "eval_chain: bias ", i, " must be contiguous fp32 [", bn[i],
-                "] on x's GPU");
-  }
+  check_biases("eval_chain", biases, x.get_device());
   const bool with_pred = want_pred || pred_out.has_value();
   TORCH_CHECK(with_pred || target.has_value(),
               "eval_chain: nothing to compute (no target, no predictions)");
@@ -1421,28 +1375,24 @@ eval_chain_bf16(const at::Tensor& x, const std::vector<at::Tensor>& Wstage,
     const int64_t Mp = (M + 31) / 32 * 32;
     auto xs = at::empty({Mp * 112}, x.options());
     launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
-    if (hw.on) {
-      launch_eval_chain_w(
-          xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
-          Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
-          Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
-          Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
-          with_pred ? pred.data_ptr<float>() : nullptr,
-          tgt.data_ptr<float>(), part.data_ptr<float>(), M, crows, ctask,
-          hist.has_value() ? hist->data_ptr<int64_t>() : nullptr, hw.weight,
-          current_stream());
-    } else {
-      launch_eval_chain(
-          xs.data_ptr(), Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
-          Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
-          Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
-          Wstage[3].data_ptr(), biases[3].data_ptr<float>(),
-          with_pred ? pred.data_ptr<float>() : nullptr,
-          target.has_value() ? tgt.data_ptr<float>() : nullptr,
-          target.has_value() ? part.data_ptr<float>() : nullptr, M, crows,
-          ctask, hist.has_value() ? hist->data_ptr<int64_t>() : nullptr,
-          current_stream());
+    EvalChainArgs p{};
+    p.x0s = xs.data_ptr();
+    p.w = {Wstage[0].data_ptr(), biases[0].data_ptr<float>(),
+           Wstage[1].data_ptr(), biases[1].data_ptr<float>(),
+           Wstage[2].data_ptr(), biases[2].data_ptr<float>(),
+           Wstage[3].data_ptr(), biases[3].data_ptr<float>()};
+    if (with_pred) p.pred = pred.data_ptr<float>();
+    if (target.has_value()) {
+      p.target = tgt.data_ptr<float>();
+      p.part = part.data_ptr<float>();
     }
+    p.M = M;
+    p.rows = crows;
+    p.task = ctask;
+    if (hist.has_value()) p.hist = hist->data_ptr<int64_t>();
+    p.weighted = hw.on;
+    p.weight = hw.weight;
+    launch_eval_chain(p, current_stream());
   }
   c10::optional<at::Tensor> po, pa;
   if (with_pred) po = pred;

@@ -36,6 +36,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "chain.h"
+
 namespace rsdl {
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short wf_bf16x8;
@@ -334,9 +336,6 @@ __global__ void __launch_bounds__(256) slab_reduce_kernel(
 
 // layer configs: 1 -> NT_W=2,KT_W=4 (dW1 [512,128pad]); 2 -> 1,8
 // (dW2 [256,512]); 3 -> 1,8 (dW3 [128,256]).
-int64_t wgrad_frag_nslabs(int64_t mchunks, int32_t N, int32_t K,
-                          int32_t nt_w, int32_t kt_w);
-
 void launch_slab_reduce(const float* part, float* out, int64_t nk,
                         int64_t nslabs, hipStream_t stream) {
   const int64_t nk4 = nk / 4;

@@ -332,58 +332,39 @@ class FusedEvaluator:
         o = out.double()
         # the kernels read the target as fp32
         t = target.reshape(-1).float().double().to(o.device)
+        # The kernels' sums in fp64 torch: every term scaled by w (the fp32
+        # weight, widened; 1 when unweighted, an exact factor), and a
+        # sixth sum for w that only the weighted accumulator keeps.
         if self.weighted:
-            self._composed_weighted(acc, hist, out, o, t,
-                                    w32.to(o.device), M)
-            return
+            w32 = w32.to(o.device)
+            w = w32.double()
+        else:
+            w = torch.ones_like(o)
+        rows = torch.full((), float(M), dtype=torch.float64,
+                          device=o.device)
         if self._binary:
             e = torch.exp(-o.abs())
             sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
             ll = torch.clamp(o, min=0.0) - o * t + torch.log1p(e)
             cls = t >= 0.5
-            acc += torch.stack([
-                torch.full((), float(M), dtype=torch.float64,
-                           device=o.device),
-                ll.sum(), ((sg - t) ** 2).sum(), t.sum(),
-                ((o >= 0) == cls).double().sum(),
-            ])
-            if hist is not None:
-                idx = cls.to(torch.int64) * HIST_BINS + logit_keys(out)
+            sums = [rows, (w * ll).sum(), (w * (sg - t) ** 2).sum(),
+                    (w * t).sum(), (w * ((o >= 0) == cls).double()).sum(),
+                    w.sum()]
+        else:
+            d = o - t
+            sums = [rows, (w * d * d).sum(), (w * d.abs()).sum(),
+                    (w * t).sum(), (w * t * t).sum(), w.sum()]
+        acc += torch.stack(sums[:self._nacc])
+        if hist is not None:
+            # integer adds either way: 1 per row, or llrint(w * 2^20)
+            # formed in fp32 as the weighted kernel forms it
+            idx = cls.to(torch.int64) * HIST_BINS + logit_keys(out)
+            if self.weighted:
+                units = torch.round(w32 * HIST_WEIGHT_SCALE).to(torch.int64)
+                hist.view(-1).index_add_(0, idx, units)
+            else:
                 hist += torch.bincount(
                     idx, minlength=2 * HIST_BINS).view(2, HIST_BINS)
-            return
-        d = o - t
-        acc += torch.stack([
-            torch.full((), float(M), dtype=torch.float64, device=o.device),
-            (d * d).sum(), d.abs().sum(), t.sum(), (t * t).sum(),
-        ])
-
-    def _composed_weighted(self, acc, hist, out, o, t, w32, M) -> None:
-        """The weighted kernel's sums in fp64 torch: every term scaled by
-        w (the fp32 weight, widened), a sixth sum for w, and the histogram
-        fed with llrint(w * 2^20) formed in fp32 as the kernel forms it."""
-        w = w32.double()
-        rows = torch.full((), float(M), dtype=torch.float64,
-                          device=o.device)
-        if not self._binary:
-            d = o - t
-            acc += torch.stack([
-                rows, (w * d * d).sum(), (w * d.abs()).sum(), (w * t).sum(),
-                (w * t * t).sum(), w.sum(),
-            ])
-            return
-        e = torch.exp(-o.abs())
-        sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
-        ll = torch.clamp(o, min=0.0) - o * t + torch.log1p(e)
-        cls = t >= 0.5
-        acc += torch.stack([
-            rows, (w * ll).sum(), (w * (sg - t) ** 2).sum(), (w * t).sum(),
-            (w * ((o >= 0) == cls).double()).sum(), w.sum(),
-        ])
-        if hist is not None:
-            idx = cls.to(torch.int64) * HIST_BINS + logit_keys(out)
-            units = torch.round(w32 * HIST_WEIGHT_SCALE).to(torch.int64)
-            hist.view(-1).index_add_(0, idx, units)
 
     def reset(self) -> None:
         if self._acc is not None:
@@ -436,60 +417,31 @@ class FusedEvaluator:
             if h is not None:
                 dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
         nan = float("nan")
+        v = v.tolist()
+        rows, c0, c1, c2, c3 = v[:5]
+        # every mean is over n: the row count, or sum w when weighted
+        n = v[5] if self.weighted else rows
+        ok = n > 0.0
+        res = {"rows": int(rows)}
         if self.weighted:
-            return self._weighted_metrics(v.tolist(), h)
-        rows, sse, sae, st, stt = v.tolist()
-        if self._binary:
-            if rows <= 0:
-                res = {"rows": 0, "logloss": nan, "accuracy": nan,
-                       "brier": nan, "base_rate": nan}
-            else:
-                res = {
-                    "rows": int(rows),
-                    "logloss": sse / rows,
-                    "accuracy": stt / rows,
-                    "brier": sae / rows,
-                    "base_rate": st / rows,
-                }
-            if h is not None:
-                res["auc"] = auc_from_hist(h)
-            return res
-        if rows <= 0:
-            return {"rows": 0, "mse": nan, "rmse": nan, "mae": nan,
-                    "r2": nan}
-        mse = sse / rows
-        den = stt - st * st / rows
-        return {
-            "rows": int(rows),
-            "mse": mse,
-            "rmse": math.sqrt(mse),
-            "mae": sae / rows,
-            "r2": 1.0 - sse / den if den != 0.0 else nan,
-        }
-
-    def _weighted_metrics(self, v, h) -> Dict[str, float]:
-        """compute() for ``weighted=True``: the means over sum w."""
-        rows, c0, c1, c2, c3, sw = v
-        nan = float("nan")
-        ok = sw > 0.0
-        res = {"rows": int(rows), "weight_sum": sw}
+            res["weight_sum"] = n
         if self._binary:
             res.update({
-                "logloss": c0 / sw if ok else nan,
-                "accuracy": c3 / sw if ok else nan,
-                "brier": c1 / sw if ok else nan,
-                "base_rate": c2 / sw if ok else nan,
+                "logloss": c0 / n if ok else nan,
+                "accuracy": c3 / n if ok else nan,
+                "brier": c1 / n if ok else nan,
+                "base_rate": c2 / n if ok else nan,
             })
             if h is not None:
                 res["auc"] = auc_from_hist(h)
             return res
-        mse = c0 / sw if ok else nan
-        den = c3 - c2 * c2 / sw if ok else 0.0
+        mse = c0 / n if ok else nan
+        den = c3 - c2 * c2 / n if ok else 0.0
         res.update({
             "mse": mse,
             "rmse": math.sqrt(mse) if ok else nan,
-            "mae": c1 / sw if ok else nan,
-            "r2": 1.0 - c0 / den if ok and den != 0.0 else nan,
+            "mae": c1 / n if ok else nan,
+            "r2": 1.0 - c0 / den if den != 0.0 else nan,
         })
         return res
 

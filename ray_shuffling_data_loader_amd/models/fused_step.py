@@ -111,29 +111,16 @@ def _loss_kw(code: int) -> dict:
     return {"loss": code} if code else {}
 
 
-def bce_head(out: torch.Tensor, target: torch.Tensor, m_rows: int):
-    """(dyb bf16 [M,1], loss_part fp32 [1]) of the BCE head in torch,
-    from the chain's bf16 ``out`` and with the kernel's formulas — for
-    stand-ins without LOSS_BCE (FakeHip forms its MSE head from the bf16
-    ``out`` the same way)."""
-    o = out.float().reshape(-1, 1)
-    t = target.float().reshape(-1, 1)
-    e = torch.exp(-o.abs())
-    sg = torch.where(o >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
-    dyb = ((1.0 / m_rows) * (sg - t)).bfloat16()
-    part = (torch.clamp(o, min=0.0) - o * t + torch.log1p(e)).sum()
-    return dyb, part.reshape(1)
-
-
 def loss_head(out: torch.Tensor, target: torch.Tensor, m_rows: int,
               loss: str = "bce", sample_weight=None, pos_weight=None):
-    """(dyb bf16 [M,1], loss_part fp32 [1]) of the weighted head in torch,
-    from the chain's bf16 ``out`` and with the kernel's formulas and
-    grouping (csrc/fwd_chain.hip, WEIGHTED) — for stand-ins without
-    HEAD_WEIGHTS. ``sample_weight`` fp32 [M] or None (every w = 1),
-    ``pos_weight`` a float or None (BCE only). Normalisation is by M.
-    With w = 1 and no pos_weight the results are those of ``bce_head`` /
-    the stand-in's own MSE head, bit for bit."""
+    """(dyb bf16 [M,1], loss_part fp32 [1]) of the head in torch, from the
+    chain's bf16 ``out`` and with the kernel's formulas and grouping
+    (csrc/fwd_chain.hip) — for stand-ins without LOSS_BCE or HEAD_WEIGHTS
+    (FakeHip forms its MSE head from the bf16 ``out`` the same way).
+    ``sample_weight`` fp32 [M] or None (every w = 1), ``pos_weight`` a
+    float or None (BCE only). Normalisation is by M. With w = 1 and no
+    pos_weight the results are those of the unweighted kernels / the
+    stand-in's own MSE head, bit for bit."""
     o = out.float().reshape(-1, 1)
     t = target.float().reshape(-1, 1).to(o.device)
     inv_m = torch.tensor(1.0 / m_rows, dtype=torch.float32, device=o.device)
@@ -160,6 +147,11 @@ def loss_head(out: torch.Tensor, target: torch.Tensor, m_rows: int,
         g = (1.0 - t) * sg - pt * torch.where(o >= 0, small, big)
     dyb = ((inv_m * w) * g).bfloat16()
     return dyb, (w * term).sum().reshape(1)
+
+
+def bce_head(out: torch.Tensor, target: torch.Tensor, m_rows: int):
+    """``loss_head`` for plain BCE: no weights, no pos_weight."""
+    return loss_head(out, target, m_rows)
 
 
 def _head_args(M: int, loss: str, sample_weight, pos_weight):
@@ -323,11 +315,8 @@ def fused_step(
             x, buf["W1p"], b1, buf["W2"], b2, buf["W3"], b3, buf["w4"], b4,
             target=None, xt_out=xt, pi16=_PI16, **_rows_kw(),
         )
-        if weighted:
-            dyb, loss_part = loss_head(out, target, M, loss_name,
-                                       sample_weight, pos_weight)
-        else:
-            dyb, loss_part = bce_head(out, target, M)
+        dyb, loss_part = loss_head(out, target, M, loss_name,
+                                   sample_weight, pos_weight)
     else:
         a1t, mask1, a2t, mask2, a3, out, dyb, loss_part = (
             hip.fwd_chain_bf16(
