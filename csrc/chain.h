@@ -94,9 +94,12 @@ void launch_bwd_chain(const BwdChainArgs& p, hipStream_t stream);
 // csrc/wgrad_frag.hip
 int64_t wgrad_frag_nslabs(int64_t mchunks, int32_t N, int32_t K,
                           int32_t nt_w, int32_t kt_w);
+// variant: 0 = default (RSDL_WGRAD_LDS, then the per-shape default),
+// 1 = direct kernel, 2 = LDS-ring kernel (12-fragment tiles only).
+bool wgrad_frag_has_lds(int32_t nt_w, int32_t kt_w);
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
-                       int32_t kt_w, hipStream_t stream);
+                       int32_t kt_w, int32_t variant, hipStream_t stream);
 void launch_slab_reduce(const float* part, float* out, int64_t nk,
                         int64_t nslabs, hipStream_t stream);
 

@@ -1001,16 +1001,44 @@ std::vector<at::Tensor> bwd_chain_bf16(
 // Per-slab fp32 partials of one fragment-major wgrad, [nslabs, N*K]:
 // buffer + launch, shared by wgrad_frag_bf16 and fused_step_bf16.
 // Requires mchunks > 0 and a tile config launch_wgrad_frag dispatches.
+// ``variant``: 0 default, 1 direct kernel, 2 LDS-ring kernel.
 at::Tensor run_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT,
                           int64_t N, int64_t K, int64_t mchunks,
-                          int64_t nt_w, int64_t kt_w) {
+                          int64_t nt_w, int64_t kt_w, int64_t variant) {
   const int64_t nslabs = wgrad_frag_nslabs(mchunks, (int32_t)N, (int32_t)K,
                                            (int32_t)nt_w, (int32_t)kt_w);
   auto part = at::empty({nslabs, N * K}, AT.options().dtype(at::kFloat));
   launch_wgrad_frag(AT.data_ptr(), BT.data_ptr(), part.data_ptr<float>(),
                     (int32_t)N, (int32_t)K, mchunks, (int32_t)nt_w,
-                    (int32_t)kt_w, current_stream());
+                    (int32_t)kt_w, (int32_t)variant, current_stream());
   return part;
+}
+
+void check_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT, int64_t N,
+                      int64_t K, int64_t mchunks, int64_t nt_w, int64_t kt_w,
+                      int64_t variant) {
+  TORCH_CHECK(AT.is_cuda() && AT.scalar_type() == at::kBFloat16 &&
+                  AT.is_contiguous() && BT.is_cuda() &&
+                  BT.scalar_type() == at::kBFloat16 && BT.is_contiguous(),
+              "wgrad_frag: inputs must be contiguous bf16 on GPU");
+  TORCH_CHECK(AT.numel() == (N / 32) * mchunks * 512,
+              "wgrad_frag: AT numel mismatch");
+  TORCH_CHECK(BT.numel() == (K / 32) * mchunks * 512,
+              "wgrad_frag: BT numel mismatch");
+  // Must list every config launch_wgrad_frag dispatches (an unlisted one
+  // would fall through its if-chain and leave the partials unwritten).
+  TORCH_CHECK((nt_w == 2 && kt_w == 4) || (nt_w == 1 && kt_w == 8) ||
+                  (nt_w == 1 && kt_w == 4),
+              "wgrad_frag: unsupported tile config");
+  TORCH_CHECK(N % (nt_w * 128) == 0 && K % (kt_w * 32) == 0,
+              "wgrad_frag: N/K not divisible by block shape");
+  TORCH_CHECK(variant >= 0 && variant <= 2,
+              "wgrad_frag: variant must be 0 (default), 1 (direct) or 2 "
+              "(LDS ring), got ", variant);
+  TORCH_CHECK(variant != 2 ||
+                  wgrad_frag_has_lds((int32_t)nt_w, (int32_t)kt_w),
+              "wgrad_frag: no LDS-ring kernel for tile config (", nt_w, ",",
+              kt_w, ")");
 }
 
 }  // namespace
@@ -1032,32 +1060,30 @@ at::Tensor swizzle_xt_bf16(const at::Tensor& x, bool pi16) {
 // inputs pre-swizzled to [C/32][Mp/16][2][32][8] fragment layout.
 at::Tensor wgrad_frag_bf16(const at::Tensor& AT, const at::Tensor& BT,
                            int64_t N, int64_t K, int64_t mchunks,
-                           int64_t nt_w, int64_t kt_w) {
-  TORCH_CHECK(AT.is_cuda() && AT.scalar_type() == at::kBFloat16 &&
-                  AT.is_contiguous() && BT.is_cuda() &&
-                  BT.scalar_type() == at::kBFloat16 && BT.is_contiguous(),
-              "wgrad_frag: inputs must be contiguous bf16 on GPU");
-  TORCH_CHECK(AT.numel() == (N / 32) * mchunks * 512,
-              "wgrad_frag: AT numel mismatch");
-  TORCH_CHECK(BT.numel() == (K / 32) * mchunks * 512,
-              "wgrad_frag: BT numel mismatch");
-  // Must list every config launch_wgrad_frag dispatches (an unlisted one
-  // would fall through its if-chain and leave the partials unwritten).
-  TORCH_CHECK((nt_w == 2 && kt_w == 4) || (nt_w == 1 && kt_w == 8) ||
-                  (nt_w == 1 && kt_w == 4),
-              "wgrad_frag: unsupported tile config");
-  TORCH_CHECK(N % (nt_w * 128) == 0 && K % (kt_w * 32) == 0,
-              "wgrad_frag: N/K not divisible by block shape");
+                           int64_t nt_w, int64_t kt_w, int64_t variant) {
+  check_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
   auto dW = at::zeros({N, K}, AT.options().dtype(at::kFloat));
   if (mchunks > 0) {
     // Per-slab fp32 partials + split-slab reduce (atomic combine over
     // <= a handful of writers per line).
-    auto part = run_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w);
+    auto part = run_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
     const int64_t nslabs = part.size(0);
     launch_slab_reduce(part.data_ptr<float>(), dW.data_ptr<float>(),
                        N * K, nslabs, current_stream());
   }
   return dW;
+}
+
+// The raw per-slab partials [nslabs, N*K] of the same launch, unreduced:
+// unlike the atomically combined output above they are bit-stable, so two
+// kernel variants can be compared with torch.equal.
+at::Tensor wgrad_frag_partials_bf16(const at::Tensor& AT,
+                                    const at::Tensor& BT, int64_t N,
+                                    int64_t K, int64_t mchunks, int64_t nt_w,
+                                    int64_t kt_w, int64_t variant) {
+  check_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
+  TORCH_CHECK(mchunks > 0, "wgrad_frag_partials: mchunks must be positive");
+  return run_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
 }
 
 // ---------------------------------------------------------------------
@@ -1249,9 +1275,12 @@ std::vector<at::Tensor> fused_step_bf16(
     const std::vector<at::Tensor>& biases, bool pi16,
     const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
     int64_t loss, const c10::optional<at::Tensor>& weight,
-    double pos_weight) {
+    double pos_weight, int64_t wgrad_variant) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fused_step", "loss");
+  TORCH_CHECK(wgrad_variant >= 0 && wgrad_variant <= 2,
+              "fused_step: wgrad_variant must be 0, 1 or 2, got ",
+              wgrad_variant);
   const HeadWeights hw =
       head_weights("fused_step", x, weight, pos_weight, closs);
   check_x("fused_step", x);
@@ -1271,9 +1300,13 @@ std::vector<at::Tensor> fused_step_bf16(
   // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
   const char* st = std::getenv("RSDL_WGRAD_SMALL_TILES");
   const int64_t kt23 = (st != nullptr && std::strcmp(st, "1") == 0) ? 4 : 8;
-  auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4);
-  auto p2 = run_wgrad_frag(b.dz2t, f.a1t, 256, 512, mchunks, 1, kt23);
-  auto p3 = run_wgrad_frag(b.dz3t, f.a2t, 128, 256, mchunks, 1, kt23);
+  // wgrad_variant 0 (what callers pass outside tests) = the default of
+  // launch_wgrad_frag. The small tiles have the direct kernel only, and
+  // the launcher keeps them on it whatever the variant.
+  const int64_t wv = wgrad_variant;  // 0 | 1 | 2, checked above
+  auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4, wv);
+  auto p2 = run_wgrad_frag(b.dz2t, f.a1t, 256, 512, mchunks, 1, kt23, wv);
+  auto p3 = run_wgrad_frag(b.dz3t, f.a2t, 128, 256, mchunks, 1, kt23, wv);
   return run_step_finalize(p1, p2, p3, b.db_part, f.loss_part, M, outs);
 }
 
@@ -1458,7 +1491,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pi16") = false);
   m.def("wgrad_frag_bf16", &rsdl::wgrad_frag_bf16, py::arg("AT"),
         py::arg("BT"), py::arg("N"), py::arg("K"), py::arg("mchunks"),
-        py::arg("nt_w"), py::arg("kt_w"));
+        py::arg("nt_w"), py::arg("kt_w"), py::arg("variant") = 0);
+  m.def("wgrad_frag_partials_bf16", &rsdl::wgrad_frag_partials_bf16,
+        py::arg("AT"), py::arg("BT"), py::arg("N"), py::arg("K"),
+        py::arg("mchunks"), py::arg("nt_w"), py::arg("kt_w"),
+        py::arg("variant") = 0);
   m.def("fwd_chain_bf16", &rsdl::fwd_chain_bf16, py::arg("x"),
         py::arg("W1"), py::arg("b1"), py::arg("W2"), py::arg("b2"),
         py::arg("W3"), py::arg("b3"), py::arg("w4"), py::arg("b4"),
@@ -1479,7 +1516,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("target"), py::arg("weights"), py::arg("biases"),
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
         py::arg("rows") = 0, py::arg("loss") = 0,
-        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0);
+        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0,
+        py::arg("wgrad_variant") = 0);
   m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
         py::arg("Wstage"), py::arg("biases"),
         py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,

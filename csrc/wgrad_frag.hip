@@ -16,7 +16,14 @@
 // for free: bwd_chain writes dz^T straight from its epilogue registers
 // and fwd_chain/swizzle_x emit src^T (round-2 stage 2/3).
 //
-// Structure: NO LDS, no barriers — per m-chunk (16 rows) each wave loads
+// Two kernels compute the same per-slab partials, bit for bit:
+// wgrad_frag_kernel (direct, below; the reference, the default for dW1
+// and the only one for the small tiles) and wgrad_lds_kernel (further
+// down; stages each chunk's unique fragments once per workgroup through
+// an LDS ring; the default for dW2 and dW3). launch_wgrad_frag picks:
+// explicit variant, then RSDL_WGRAD_LDS, then the per-shape default.
+//
+// Direct kernel: NO LDS, no barriers — per m-chunk (16 rows) each wave loads
 // its (NT_W + KT_W) fragments directly from global (coalesced; waves of
 // one workgroup share B blocks -> L1 hits) and issues NT_W*KT_W MFMAs,
 // 3-deep prefetched, consumed in reverse load order so the final wait
@@ -239,6 +246,173 @@ __global__ void __launch_bounds__(256, MIN_WAVES) wgrad_frag_kernel(
   }
 }
 
+// LDS-ring variant of wgrad_frag_kernel: same tile, grid, slab partition,
+// XCD decode, MFMAs and epilogue, but the workgroup stages each chunk's
+// 12 UNIQUE fragments (4*NT_W of A + KT_W of B, 12 KB) once into a ring
+// of kLdsStages LDS stages instead of every wave loading all B fragments
+// itself. The fragment layout [2][32][8] is lane-linear at 16 B per lane,
+// i.e. exactly the image global_load_lds_dwordx4 writes, so each wave
+// issues 3 LDS-DMA loads per chunk (9 register loads in the direct
+// kernel) and no prefetch state lives in registers.
+//
+// Pipeline, per chunk i (stage i % S):
+//   s_waitcnt vmcnt(3 * chunks left in flight) lgkmcnt(0)
+//       this wave's three DMAs of chunk i have landed, and its ds_reads
+//       of chunk i-1 are complete;
+//   s_barrier
+//       every wave's share of chunk i is in LDS, and nobody still reads
+//       stage (i-1) % S;
+//   issue the DMAs of chunk i+S-1 into stage (i-1) % S;
+//   ds_read_b128 this wave's NT_W + KT_W fragments of chunk i; MFMAs.
+// S-2 stages stay in flight ACROSS the barrier (S-1 after the issue),
+// hence the raw s_barrier with a counted vmcnt: __syncthreads() would
+// drain the DMAs with vmcnt(0). All loads of the loop are LDS-DMA and the
+// ring is the kernel's only __shared__ object, so the compiler adds no
+// vmcnt(0) of its own. Every acc[nt][kt] sees the same MFMA on the same
+// operands in the same chunk order as in wgrad_frag_kernel: the partials
+// are bit-identical.
+constexpr int kLdsStages = 6;          // 6 x 12 KB = 72 KB: 2 workgroups/CU
+constexpr int kLdsStageElems = 12 * 512;
+
+#define WL_WAIT(n) \
+  asm volatile("s_waitcnt vmcnt(" #n ") lgkmcnt(0)" ::: "memory")
+
+template <int NT_W, int KT_W>
+__global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
+    const short* __restrict__ AT, const short* __restrict__ BT,
+    float* __restrict__ dW,  // [nslabs][N,K] fp32 partials
+    int32_t N, int32_t K, int64_t mchunks, int32_t nblk_n, int32_t nblk_k,
+    int64_t nslabs, int64_t chunks_per_slab) {
+  constexpr int S = kLdsStages;
+  constexpr int P = S - 1;      // chunks issued ahead of the consumer
+  constexpr int NA = 4 * NT_W;  // A fragments per chunk
+  static_assert(NA + KT_W == 12, "a stage is 12 fragments, 3 per wave");
+  static_assert(P - 1 == 4, "WL_WAIT counts below assume S == 6");
+  __shared__ __attribute__((aligned(16))) short ring[S * kLdsStageElems];
+
+  const int32_t NBLK = (nblk_n < 0 ? -nblk_n : nblk_n) * nblk_k;
+  int64_t slab;
+  int32_t blk;
+  if (nblk_n < 0) {  // linear decode (A/B: RSDL_WGRAD_LINEAR)
+    nblk_n = -nblk_n;
+    blk = (int32_t)(blockIdx.x % (uint32_t)NBLK);
+    slab = blockIdx.x / (uint32_t)NBLK;
+  } else {
+    const int32_t xcd = blockIdx.x & 7;
+    const int32_t g = blockIdx.x >> 3;
+    blk = g % NBLK;
+    slab = (int64_t)(g / NBLK) * 8 + xcd;
+  }
+  // Both returns are workgroup-uniform and ahead of the first barrier.
+  if (slab >= nslabs) return;
+  const int32_t bn = blk / nblk_k;
+  const int32_t bk = blk % nblk_k;
+  const int64_t c0 = slab * chunks_per_slab;
+  const int64_t cend = min(c0 + chunks_per_slab, mchunks);
+  if (c0 >= cend) return;
+  const int64_t iters = cend - c0;
+
+  const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t lane = threadIdx.x & 63;
+  const int32_t nt0 = bn * NA + wave * NT_W;
+  const int32_t kt0 = bk * KT_W;
+
+  // Loader role: fragments 3*wave .. 3*wave+2 of the stage (A first).
+  const short* gp[3];
+  #pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const int32_t f = wave * 3 + j;
+    const short* base =
+        f < NA ? AT + ((int64_t)(bn * NA + f) * mchunks + c0) * 512
+               : BT + ((int64_t)(kt0 + f - NA) * mchunks + c0) * 512;
+    gp[j] = base + lane * 8;
+  }
+
+  wf_f32x16 acc[NT_W][KT_W] = {};
+
+// One chunk's three DMAs of this wave into stage `st`; the LDS address
+// is the wave-uniform fragment base (the hardware adds lane * 16).
+#define WL_ISSUE(st)                                                       \
+  {                                                                        \
+    _Pragma("unroll") for (int j = 0; j < 3; j++) {                        \
+      __builtin_amdgcn_global_load_lds(                                    \
+          (const __attribute__((address_space(1))) void*)gp[j],            \
+          (__attribute__((address_space(3))) void*)(                       \
+              ring + (st) * kLdsStageElems + (wave * 3 + j) * 512),        \
+          16, 0, 0);                                                       \
+      gp[j] += 512;                                                        \
+    }                                                                      \
+  }
+#define WL_CONSUME(st)                                                     \
+  {                                                                        \
+    const short* sp = ring + (st) * kLdsStageElems + lane * 8;             \
+    wf_bf16x8 a[NT_W], b[KT_W];                                            \
+    _Pragma("unroll") for (int nt = 0; nt < NT_W; nt++) {                  \
+      a[nt] = *reinterpret_cast<const wf_bf16x8*>(                         \
+          sp + (wave * NT_W + nt) * 512);                                  \
+    }                                                                      \
+    _Pragma("unroll") for (int kt = 0; kt < KT_W; kt++) {                  \
+      b[kt] = *reinterpret_cast<const wf_bf16x8*>(sp + (NA + kt) * 512);   \
+    }                                                                      \
+    _Pragma("unroll") for (int nt = 0; nt < NT_W; nt++) {                  \
+      _Pragma("unroll") for (int kt = 0; kt < KT_W; kt++) {                \
+        acc[nt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(             \
+            a[nt], b[kt], acc[nt][kt], 0, 0, 0);                           \
+      }                                                                    \
+    }                                                                      \
+  }
+
+  int32_t ws = 0, rs = 0;  // next stage to fill / to consume
+  const int64_t pre = iters < P ? iters : P;
+  for (int64_t j = 0; j < pre; j++) {
+    WL_ISSUE(ws);
+    ws = ws + 1 == S ? 0 : ws + 1;
+  }
+  int64_t i = 0;
+  // Steady state: chunks i .. i+P-1 are in flight; retire chunk i and
+  // leave the P-1 newer ones (3 DMAs each) outstanding.
+  for (; i + P < iters; i++) {
+    WL_WAIT(12);
+    __builtin_amdgcn_s_barrier();
+    WL_ISSUE(ws);
+    ws = ws + 1 == S ? 0 : ws + 1;
+    WL_CONSUME(rs);
+    rs = rs + 1 == S ? 0 : rs + 1;
+  }
+  // Drain: every chunk is issued; iters-1-i (<= P-1) are newer than i.
+  for (; i < iters; i++) {
+    switch (iters - 1 - i) {
+      case 0: WL_WAIT(0); break;
+      case 1: WL_WAIT(3); break;
+      case 2: WL_WAIT(6); break;
+      case 3: WL_WAIT(9); break;
+      default: WL_WAIT(12); break;
+    }
+    __builtin_amdgcn_s_barrier();
+    WL_CONSUME(rs);
+    rs = rs + 1 == S ? 0 : rs + 1;
+  }
+#undef WL_ISSUE
+#undef WL_CONSUME
+
+  // Epilogue: as in wgrad_frag_kernel.
+  float* part = dW + slab * (int64_t)N * K;
+  #pragma unroll
+  for (int nt = 0; nt < NT_W; nt++) {
+    #pragma unroll
+    for (int kt = 0; kt < KT_W; kt++) {
+      const int32_t k = (kt0 + kt) * 32 + (lane & 31);
+      #pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int32_t n = (nt0 + nt) * 32 + (reg & 3) + 8 * (reg >> 2) +
+                          4 * (lane >> 5);
+        part[(int64_t)n * K + k] = acc[nt][kt][reg];
+      }
+    }
+  }
+}
+#undef WL_WAIT
+
 // out[i] = sum_s part[s][i] — the slab-partial reduction (fp32, float4).
 // 2-D grid: y splits the slab range so small outputs still fill the
 // chip; the few split partials combine with fp32 atomics (<= NSPLIT
@@ -373,9 +547,47 @@ int64_t wgrad_frag_nslabs(int64_t mchunks, int32_t N, int32_t K,
   return (mchunks + cps - 1) / cps;
 }
 
+// Kernel variant of launch_wgrad_frag: 1 = direct (wgrad_frag_kernel),
+// 2 = LDS ring (wgrad_lds_kernel), 0 = the default: RSDL_WGRAD_LDS (0 or
+// 1, read once) if set, else the per-shape default below, as measured at
+// the flagship shapes (profiles/PERF.md, round 9). The ring kernel exists
+// for the 12-fragment tiles only; the default never picks it elsewhere,
+// and RSDL_WGRAD_SCHED=1 (the fenced direct kernels) keeps its meaning:
+// with it the per-shape default is the direct kernel.
+#ifndef RSDL_WGRAD_LDS_DEFAULT_DW1
+#define RSDL_WGRAD_LDS_DEFAULT_DW1 0  // [512,128], <2,4>
+#endif
+#ifndef RSDL_WGRAD_LDS_DEFAULT_DW2
+#define RSDL_WGRAD_LDS_DEFAULT_DW2 1  // [256,512], <1,8>
+#endif
+#ifndef RSDL_WGRAD_LDS_DEFAULT_DW3
+#define RSDL_WGRAD_LDS_DEFAULT_DW3 1  // [128,256] and other <1,8> shapes
+#endif
+
+bool wgrad_frag_has_lds(int32_t nt_w, int32_t kt_w) {
+  return (nt_w == 2 && kt_w == 4) || (nt_w == 1 && kt_w == 8);
+}
+
+static bool wgrad_use_lds(int32_t variant, int32_t K, int32_t nt_w,
+                          int32_t kt_w, bool sched) {
+  if (!wgrad_frag_has_lds(nt_w, kt_w)) return false;
+  if (variant != 0) return variant == 2;
+  static const int env = [] {
+    const char* e = std::getenv("RSDL_WGRAD_LDS");
+    return (e != nullptr && (e[0] == '0' || e[0] == '1') && e[1] == '\0')
+               ? e[0] - '0'
+               : -1;
+  }();
+  if (env >= 0) return env == 1;
+  if (sched) return false;
+  if (nt_w == 2) return RSDL_WGRAD_LDS_DEFAULT_DW1 != 0;
+  return (K >= 512 ? RSDL_WGRAD_LDS_DEFAULT_DW2
+                   : RSDL_WGRAD_LDS_DEFAULT_DW3) != 0;
+}
+
 void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t K, int64_t mchunks, int32_t nt_w,
-                       int32_t kt_w, hipStream_t stream) {
+                       int32_t kt_w, int32_t variant, hipStream_t stream) {
   const int32_t nblk_n = N / (nt_w * 128);
   const int32_t nblk_k = K / (kt_w * 32);
   const int32_t nblk = nblk_n * nblk_k;
@@ -398,7 +610,13 @@ void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
   const int64_t grid =
       linear ? nslabs * nblk : ((nslabs + 7) / 8) * 8 * nblk;
   const int32_t nb_n = linear ? -nblk_n : nblk_n;
-  if (nt_w == 2 && kt_w == 4) {
+  if (wgrad_use_lds(variant, K, nt_w, kt_w, sched)) {
+    auto kern = nt_w == 2 ? wgrad_lds_kernel<2, 4> : wgrad_lds_kernel<1, 8>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, stream,
+                       reinterpret_cast<const short*>(AT),
+                       reinterpret_cast<const short*>(BT), dW, N, K, mchunks,
+                       nb_n, nblk_k, nslabs, chunks_per_slab);
+  } else if (nt_w == 2 && kt_w == 4) {
     auto kern = sched ? wgrad_frag_kernel<2, 4, 2, 1>
                       : wgrad_frag_kernel<2, 4>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)grid),

@@ -52,6 +52,13 @@ _PI16 = os.environ.get("RSDL_PI16", "0") == "1"
 # build's default). Tests may override via fused_step._CHAIN_ROWS.
 _CHAIN_ROWS = int(os.environ.get("RSDL_CHAIN_ROWS", "0") or "0")
 
+# Kernel variant of the three fragment wgrads (csrc/wgrad_frag.hip):
+# 0 = the extension's default (its RSDL_WGRAD_LDS latch, then the
+# per-shape default), 1 = the direct kernel, 2 = the LDS-ring kernel for
+# all three. The partials are bit-identical either way. Tests may
+# override via fused_step._WGRAD_VARIANT.
+_WGRAD_VARIANT = 0
+
 # Native glue (default on; RSDL_NATIVE_GLUE=0 or fused_step._NATIVE_GLUE =
 # False forces the composed path): the whole schedule runs inside one
 # extension call, hip.fused_step_bf16, with the weight staging and the
@@ -198,6 +205,12 @@ def _rows_kw() -> dict:
     return {"rows": _CHAIN_ROWS} if _CHAIN_ROWS else {}
 
 
+def _wgrad_kw() -> dict:
+    """``wgrad_variant=`` for hip.fused_step_bf16; empty at the default,
+    as _rows_kw is."""
+    return {"wgrad_variant": _WGRAD_VARIANT} if _WGRAD_VARIANT else {}
+
+
 def _native_ok(hip, lin, x, target, grad_hook) -> bool:
     """Whether this call can take hip.fused_step_bf16: the extension has
     it, no staged grad_hook, and the stock fp32 model plus a bf16 batch
@@ -288,7 +301,7 @@ def fused_step(
                 [m.weight.detach() for m in lin],
                 [m.bias.detach() for m in lin],
                 pi16=_PI16, outs=outs, **_rows_kw(), **_loss_kw(loss_code),
-                **_weight_kw(sample_weight, pos_weight),
+                **_weight_kw(sample_weight, pos_weight), **_wgrad_kw(),
             )
             if outs is None:
                 # dW1..dW4 then db1..db4, fresh fp32 tensors in the
@@ -350,15 +363,15 @@ def fused_step(
         grad_hook("bias")
     # Weight grads: fragment-major MFMA wgrad kernel (csrc/wgrad_frag.hip)
     # reading the transposed fragments the producers emitted.
-    dw1 = wgrad_frag(dz1t, xt, 512, 128, mchunks)[:, :100].contiguous()
+    dw1 = wgrad_frag(dz1t, xt, 512, 128, mchunks, _WGRAD_VARIANT)[:, :100].contiguous()
     if flat_mode and grad_hook is not None:
         lin[0].weight.grad.copy_(dw1)
         grad_hook("w1")
-    dw2 = wgrad_frag(dz2t, a1t, 256, 512, mchunks)
+    dw2 = wgrad_frag(dz2t, a1t, 256, 512, mchunks, _WGRAD_VARIANT)
     if flat_mode and grad_hook is not None:
         lin[1].weight.grad.copy_(dw2)
         grad_hook("w2")
-    dw3 = wgrad_frag(dz3t, a2t, 128, 256, mchunks)
+    dw3 = wgrad_frag(dz3t, a2t, 128, 256, mchunks, _WGRAD_VARIANT)
     if flat_mode and grad_hook is not None:
         lin[2].weight.grad.copy_(dw3)
         grad_hook("w3")

@@ -558,8 +558,12 @@ _WGRAD_FRAG_SMALL = {
 
 
 def wgrad_frag(at_frag: torch.Tensor, bt_frag: torch.Tensor, n: int,
-               k: int, mchunks: int) -> torch.Tensor:
-    """dW = dz^T @ src from pre-swizzled fragment inputs (fp32 [N,K])."""
+               k: int, mchunks: int, variant: int = 0) -> torch.Tensor:
+    """dW = dz^T @ src from pre-swizzled fragment inputs (fp32 [N,K]).
+    ``variant``: 0 = the extension's default (RSDL_WGRAD_LDS, then the
+    per-shape default), 1 = the direct kernel, 2 = the LDS-ring kernel
+    (csrc/wgrad_frag.hip). Passed on only when non-zero, so stand-ins
+    that predate the argument stay callable."""
     cfg = (
         _WGRAD_FRAG_SMALL
         if os.environ.get("RSDL_WGRAD_SMALL_TILES", "0") == "1"
@@ -567,7 +571,9 @@ def wgrad_frag(at_frag: torch.Tensor, bt_frag: torch.Tensor, n: int,
     )
     nt_w, kt_w = cfg[(n, k)]
     hip = _load_hip()
-    return hip.wgrad_frag_bf16(at_frag, bt_frag, n, k, mchunks, nt_w, kt_w)
+    kw = {"variant": variant} if variant else {}
+    return hip.wgrad_frag_bf16(at_frag, bt_frag, n, k, mchunks, nt_w, kt_w,
+                               **kw)
 
 
 def t_frag_unswizzle(

@@ -1,14 +1,30 @@
 #!/usr/bin/env python3
 """Time the fragment-major wgrad path (wgrad_frag kernel + slab_reduce)
 at the three flagship shapes. A/B the pinned-schedule variants with
-RSDL_WGRAD_SCHED=1 (see profiles/r02/wgrad_sched_asm.md)."""
+RSDL_WGRAD_SCHED=1 (see profiles/r02/wgrad_sched_asm.md).
+
+``--ab [ROUNDS]`` instead times the wgrad kernel ALONE (the raw slab
+partials, no zero-fill and no slab_reduce), alternating the direct
+kernel (variant 1) and the LDS-ring kernel (variant 2) in one process,
+and applies the rule a per-shape default has to pass: every ring timing
+below every direct timing, and the median difference at least three
+times the larger within-variant spread. One JSON line per shape."""
+import argparse
+import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from ray_shuffling_data_loader_amd.ops.shuffle_ops import wgrad_frag  # noqa: E402
+from ray_shuffling_data_loader_amd.ops.shuffle_ops import (  # noqa: E402
+    _WGRAD_FRAG_CFG,
+    _load_hip,
+    wgrad_frag,
+)
+
+SHAPES = [(512, 128), (256, 512), (128, 256)]  # (N, K) of dW1, dW2, dW3
 
 
 def t(fn, iters=50, warmup=5):
@@ -25,15 +41,69 @@ def t(fn, iters=50, warmup=5):
     return a.elapsed_time(b) / iters
 
 
-def main():
-    M = 250_000
+def inputs(N, K, mchunks, dev="cuda"):
+    # AT is dz^T [N-tiles][mchunks][512], BT is src^T.
+    at = torch.randn(N // 32 * mchunks * 512, device=dev).bfloat16()
+    bt = torch.randn(K // 32 * mchunks * 512, device=dev).bfloat16()
+    return at, bt
+
+
+def ab(M, rounds):
+    hip = _load_hip()
     mchunks = 2 * ((M + 31) // 32)
-    dev = "cuda"
+    for N, K in SHAPES:
+        nt_w, kt_w = _WGRAD_FRAG_CFG[(N, K)]
+        at, bt = inputs(N, K, mchunks)
+        us = {1: [], 2: []}
+        nslabs = 0
+        # round -1 is a discarded warm-up pair: the first timing after
+        # the inputs are generated runs while the clocks still settle
+        for r in range(-1, rounds):
+            for v in (1, 2):
+                def run():
+                    return hip.wgrad_frag_partials_bf16(
+                        at, bt, N, K, mchunks, nt_w, kt_w, variant=v)
+                nslabs = run().shape[0]
+                us_v = t(run) * 1e3
+                if r >= 0:
+                    us[v].append(us_v)
+        # unique bytes: A^T + B^T fragments once (the re-reads by the
+        # other output blocks of a slab are meant to hit in L2), plus
+        # the fp32 partials written
+        by = (at.numel() + bt.numel()) * 2 + nslabs * N * K * 4
+        med = {v: statistics.median(us[v]) for v in us}
+        spread = max(max(us[v]) - min(us[v]) for v in us)
+        diff = med[1] - med[2]
+        passes = max(us[2]) < min(us[1]) and diff >= 3 * spread
+        print(json.dumps({
+            "shape": [N, K], "tile": [nt_w, kt_w], "M": M,
+            "direct_us": [round(x, 2) for x in us[1]],
+            "lds_us": [round(x, 2) for x in us[2]],
+            "direct_med_us": round(med[1], 2),
+            "lds_med_us": round(med[2], 2),
+            "direct_TBps": round(by / med[1] / 1e6, 2),
+            "lds_TBps": round(by / med[2] / 1e6, 2),
+            "bytes_MB": round(by / 1e6, 1),
+            "median_diff_us": round(diff, 2),
+            "max_spread_us": round(spread, 2),
+            "lds_passes_rule": passes,
+        }), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--ab", type=int, nargs="?", const=5, default=0,
+                   metavar="ROUNDS")
+    p.add_argument("--rows", type=int, default=250_000)
+    args = p.parse_args()
+    M = args.rows
+    if args.ab:
+        ab(M, args.ab)
+        return
+    mchunks = 2 * ((M + 31) // 32)
     print(f"RSDL_WGRAD_SCHED={os.environ.get('RSDL_WGRAD_SCHED', '0')}")
-    # (N, K) of dW; AT is dz^T [N-tiles][mchunks][512], BT is src^T.
-    for N, K in [(512, 128), (256, 512), (128, 256)]:
-        at = torch.randn(N // 32 * mchunks * 512, device=dev).bfloat16()
-        bt = torch.randn(K // 32 * mchunks * 512, device=dev).bfloat16()
+    for N, K in SHAPES:
+        at, bt = inputs(N, K, mchunks)
         ms = t(lambda: wgrad_frag(at, bt, N, K, mchunks))
         by = (at.numel() + bt.numel()) * 2  # bf16 stream bytes
         print(
