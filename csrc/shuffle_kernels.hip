@@ -114,9 +114,16 @@ template <>
 __device__ __forceinline__ __hip_bfloat16 cast_elem(float v) {
   return __float2bfloat16(v);
 }
+// ONE rounding, double -> bf16. Written as __float2bfloat16((float)v) this
+// always compiled to the same thing (the compiler folds two adjacent
+// truncations into one), so the bits are what they were; spelling it out
+// keeps them from depending on whether the two casts stay adjacent in a
+// caller. It differs from rounding to fp32 first only where the fp32 value
+// is a bf16 tie (about 2^-17 of random inputs). The standardized paths do
+// round to fp32 first: affine_f32 returns a float by definition.
 template <>
 __device__ __forceinline__ __hip_bfloat16 cast_elem(double v) {
-  return __float2bfloat16((float)v);
+  return __double2bfloat16(v);
 }
 template <>
 __device__ __forceinline__ __hip_bfloat16 cast_elem(int32_t v) {
@@ -229,6 +236,66 @@ __device__ void pack_col_loop(
   }
 }
 
+// Same-dtype column (src_dtype == dst_dtype): a byte copy, whatever the
+// dtype — this is how bf16/f16 columns of a narrowed source block (see
+// narrow_rows_kernel) are unpacked. Every address is base + row * pitch +
+// j * sizeof(V), so V may be as wide as the two bases, the two pitches and
+// the column's byte width all prove, and no wider. The flagship narrow row
+// (200 B of bf16 features at offset 8 of a 208-B row -> a 200-B pitch
+// matrix) proves 8 B: 25 lanes per row.
+template <typename V>
+__device__ __forceinline__ void copy_col_loop(
+    const uint8_t* __restrict__ src, int64_t src_pitch,
+    const int64_t* __restrict__ perm, uint8_t* __restrict__ dst,
+    int64_t dst_pitch, int32_t col_bytes, int64_t n_rows, int64_t tid,
+    int64_t nthreads) {
+  const int32_t lanes = col_bytes / (int32_t)sizeof(V);
+  const int64_t total = n_rows * lanes;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / lanes;
+    const int64_t j = i - row * lanes;
+    const int64_t srow = perm ? perm[row] : row;
+    const V v = *reinterpret_cast<const V*>(
+        src + srow * src_pitch + j * (int64_t)sizeof(V));
+    *reinterpret_cast<V*>(dst + row * dst_pitch + j * (int64_t)sizeof(V)) = v;
+  }
+}
+
+__device__ __forceinline__ void copy_col(
+    const uint8_t* __restrict__ src, int64_t src_pitch,
+    const int64_t* __restrict__ perm, uint8_t* __restrict__ dst,
+    int64_t dst_pitch, int32_t col_bytes, int64_t n_rows, int64_t tid,
+    int64_t nthreads) {
+  const uintptr_t m = reinterpret_cast<uintptr_t>(src) |
+                      reinterpret_cast<uintptr_t>(dst) |
+                      (uintptr_t)src_pitch | (uintptr_t)dst_pitch |
+                      (uintptr_t)col_bytes;
+  if ((m & 15) == 0)
+    copy_col_loop<uint4>(src, src_pitch, perm, dst, dst_pitch, col_bytes,
+                         n_rows, tid, nthreads);
+  else if ((m & 7) == 0)
+    copy_col_loop<uint2>(src, src_pitch, perm, dst, dst_pitch, col_bytes,
+                         n_rows, tid, nthreads);
+  else if ((m & 3) == 0)
+    copy_col_loop<uint32_t>(src, src_pitch, perm, dst, dst_pitch, col_bytes,
+                            n_rows, tid, nthreads);
+  else if ((m & 1) == 0)
+    copy_col_loop<uint16_t>(src, src_pitch, perm, dst, dst_pitch, col_bytes,
+                            n_rows, tid, nthreads);
+  else
+    copy_col_loop<uint8_t>(src, src_pitch, perm, dst, dst_pitch, col_bytes,
+                           n_rows, tid, nthreads);
+}
+
+__device__ __forceinline__ int32_t dtype_size(int32_t dt) {
+  switch (dt) {
+    case DT_F64: case DT_I64: return 8;
+    case DT_F32: case DT_I32: return 4;
+    case DT_F16: case DT_BF16: return 2;
+    default: return 1;
+  }
+}
+
 #define RSDL_DISPATCH_DST(S_CTYPE, SRC_DT, DST_DT, CALL)                   \
   switch (DST_DT) {                                                        \
     case DT_F32: { using D = float; CALL; break; }                         \
@@ -284,11 +351,65 @@ __global__ void unpack_permute_kernel(
       return;
     }
   }
+  if (d.src_dtype == d.dst_dtype) {
+    const int32_t col_bytes = d.numel * dtype_size(d.src_dtype);
+    copy_col(packed + d.packed_off, row_stride, perm,
+             reinterpret_cast<uint8_t*>(d.col_ptr), col_bytes, col_bytes,
+             n_rows, tid, nthreads);
+    return;
+  }
   RSDL_DISPATCH_PAIR(
       d.src_dtype, d.dst_dtype,
       (unpack_col_loop<S, D>(packed, row_stride, perm,
                              reinterpret_cast<D*>(d.col_ptr), d.packed_off,
                              d.numel, n_rows, tid, nthreads)));
+}
+
+// Row-major sweep for a block whose columns are all same-dtype copies made
+// of whole 8-B lanes (the narrowed source block): one pass over the rows
+// serves every column, as gather_rows does, so a narrow scalar column (the
+// 8-B label) does not fetch the sectors of its row a second time in a pass
+// of its own. Lane j of a row belongs to the column whose [lane0, lane0 +
+// lanes) holds it; lanes in no column (padding) are skipped.
+#define RSDL_SWEEP_MAX_COLS 8
+
+struct SweepCol {
+  int64_t col_ptr;  // contiguous column tensor, 8-B aligned
+  int32_t lane0;    // packed offset / 8
+  int32_t lanes;    // column bytes per row / 8
+};
+
+struct SweepTable {
+  SweepCol cols[RSDL_SWEEP_MAX_COLS];
+};
+
+__global__ void unpack_rows_sweep_kernel(
+    const uint2* __restrict__ packed,
+    int64_t row_u2,  // row stride in 8-B lanes
+    const int64_t* __restrict__ perm,
+    SweepTable table,
+    int32_t num_cols,
+    int32_t lanes_per_row,  // lanes up to the end of the last column
+    int64_t n_rows) {
+  const int64_t total = n_rows * lanes_per_row;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    const int64_t row = i / lanes_per_row;
+    const int32_t j = (int32_t)(i - row * lanes_per_row);
+    const int64_t srow = perm ? perm[row] : row;
+#pragma unroll
+    for (int32_t c = 0; c < RSDL_SWEEP_MAX_COLS; ++c) {
+      if (c < num_cols) {
+        const SweepCol d = table.cols[c];
+        const int32_t k = j - d.lane0;
+        if ((uint32_t)k < (uint32_t)d.lanes) {
+          reinterpret_cast<uint2*>(d.col_ptr)[row * d.lanes + k] =
+              packed[srow * row_u2 + j];
+        }
+      }
+    }
+  }
 }
 
 __global__ void pack_columns_kernel(
@@ -948,6 +1069,13 @@ __global__ void unpack_permute_affine_kernel(
         return;
       }
     }
+    if (d.src_dtype == d.dst_dtype) {
+      const int32_t col_bytes = d.numel * dtype_size(d.src_dtype);
+      copy_col(packed + d.packed_off, row_stride, perm,
+               reinterpret_cast<uint8_t*>(d.col_ptr), col_bytes, col_bytes,
+               n_rows, tid, nthreads);
+      return;
+    }
     RSDL_DISPATCH_PAIR(
         d.src_dtype, d.dst_dtype,
         (unpack_col_loop<S, D>(packed, row_stride, perm,
@@ -1001,6 +1129,252 @@ __global__ void unpack_permute_affine_kernel(
                                     reinterpret_cast<D*>(d.col_ptr), aff,
                                     d.packed_off, d.numel, n_rows, tid,
                                     nthreads, fill, fill_f)));
+}
+
+// ---------------------------------------------------------------------------
+// Narrowed source cache (ShuffleEngine, RSDL_NARROW_CACHE).
+//
+// The cast (and the affine) of the fused unpack is per element and the
+// source block never changes, so cast(row[perm[i]]) every epoch equals
+// cast(row)[perm[i]] with the cast done ONCE. narrow_rows_kernel converts
+// the wide packed block to a packed block of the OUTPUT dtypes in identity
+// row order; each epoch then unpacks the narrow block with plain same-dtype
+// copies (copy_col / unpack_rows_sweep_kernel above). The arithmetic is the
+// unpack kernels' own (affine_f32, cast_elem, store4), so the bits are too.
+// ---------------------------------------------------------------------------
+
+struct NarrowCol {
+  int32_t src_off;    // byte offset inside a wide row
+  int32_t dst_off;    // byte offset inside a narrow row
+  int32_t src_dtype;
+  int32_t dst_dtype;
+  int32_t numel;
+  int32_t aff_base;   // element 0 in the (shift, scale) table, or -1
+};
+
+struct NarrowTable {
+  NarrowCol cols[RSDL_MAX_COLS];
+};
+
+// Four source elements of one lane. WIDE: 16-B loads (the address is 16-B
+// aligned); otherwise 8-B loads (it is 8-B aligned).
+template <typename S, bool WIDE>
+__device__ __forceinline__ void load4(const uint8_t* __restrict__ sp,
+                                      S (&x)[4]) {
+  if constexpr (sizeof(S) == 8) {
+    if constexpr (WIDE) {
+      const double2 v0 = reinterpret_cast<const double2*>(sp)[0];
+      const double2 v1 = reinterpret_cast<const double2*>(sp)[1];
+      x[0] = v0.x; x[1] = v0.y; x[2] = v1.x; x[3] = v1.y;
+    } else {
+      const double* dp = reinterpret_cast<const double*>(sp);
+      x[0] = dp[0]; x[1] = dp[1]; x[2] = dp[2]; x[3] = dp[3];
+    }
+  } else {
+    if constexpr (WIDE) {
+      const float4 v = *reinterpret_cast<const float4*>(sp);
+      x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    } else {
+      const float2 v0 = reinterpret_cast<const float2*>(sp)[0];
+      const float2 v1 = reinterpret_cast<const float2*>(sp)[1];
+      x[0] = v0.x; x[1] = v0.y; x[2] = v1.x; x[3] = v1.y;
+    }
+  }
+}
+
+// f64 / f32 source, f32 / bf16 destination, numel % 4 == 0: four elements
+// per lane, one packed 8-B (bf16) or 16-B (f32) store. AFF: the affine and
+// then the fp32 -> dst conversion, as unpack_affine_vec4_*; otherwise
+// cast_elem<S, D> on the source element itself, as unpack_col_loop (the two
+// are separate instantiations on purpose: a double -> bf16 cast must stay
+// the single rounding it is there).
+template <typename S, typename D, bool WIDE, bool AFF>
+__device__ __forceinline__ void narrow_vec4_loop(
+    const uint8_t* __restrict__ src, int64_t src_stride,
+    uint8_t* __restrict__ dst, int64_t dst_stride,
+    const double2* __restrict__ aff, int32_t numel, int64_t n_rows,
+    int64_t tid, int64_t nthreads, bool fill, float fill_f) {
+  const int32_t groups = numel >> 2;
+  const int64_t total = n_rows * groups;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / groups;
+    const int64_t g = i - row * groups;
+    S x[4];
+    load4<S, WIDE>(src + row * src_stride + g * (int64_t)(4 * sizeof(S)), x);
+    D* dp = reinterpret_cast<D*>(dst + row * dst_stride) + (g << 2);
+    if constexpr (AFF) {
+      const double2* ap = aff + (g << 2);
+      store4<D>(dp, affine_f32((double)x[0], ap[0], fill, fill_f),
+                affine_f32((double)x[1], ap[1], fill, fill_f),
+                affine_f32((double)x[2], ap[2], fill, fill_f),
+                affine_f32((double)x[3], ap[3], fill, fill_f));
+    } else {
+      union {
+        D h[4];
+        uint32_t u[sizeof(D)];  // 4 * sizeof(D) bytes
+      } o;
+#pragma unroll
+      for (int32_t k = 0; k < 4; ++k) o.h[k] = cast_elem<S, D>(x[k]);
+      if constexpr (sizeof(D) == 2)
+        *reinterpret_cast<uint2*>(dp) = make_uint2(o.u[0], o.u[1]);
+      else
+        *reinterpret_cast<uint4*>(dp) =
+            make_uint4(o.u[0], o.u[1], o.u[2], o.u[3]);
+    }
+  }
+}
+
+template <typename S, typename D>
+__device__ __forceinline__ void narrow_vec4(
+    const uint8_t* __restrict__ src, int64_t src_stride,
+    uint8_t* __restrict__ dst, int64_t dst_stride,
+    const double2* __restrict__ aff, int32_t numel, int64_t n_rows,
+    int64_t tid, int64_t nthreads, bool fill, float fill_f, bool wide) {
+  if (aff != nullptr) {
+    if (wide)
+      narrow_vec4_loop<S, D, true, true>(src, src_stride, dst, dst_stride,
+                                         aff, numel, n_rows, tid, nthreads,
+                                         fill, fill_f);
+    else
+      narrow_vec4_loop<S, D, false, true>(src, src_stride, dst, dst_stride,
+                                          aff, numel, n_rows, tid, nthreads,
+                                          fill, fill_f);
+  } else {
+    if (wide)
+      narrow_vec4_loop<S, D, true, false>(src, src_stride, dst, dst_stride,
+                                          aff, numel, n_rows, tid, nthreads,
+                                          fill, fill_f);
+    else
+      narrow_vec4_loop<S, D, false, false>(src, src_stride, dst, dst_stride,
+                                           aff, numel, n_rows, tid, nthreads,
+                                           fill, fill_f);
+  }
+}
+
+// Scalar fallback: any supported dtype pair, any numel, any alignment.
+template <typename S, typename D>
+__device__ void narrow_col_loop(
+    const uint8_t* __restrict__ src, int64_t src_stride,
+    uint8_t* __restrict__ dst, int64_t dst_stride,
+    const double2* __restrict__ aff, int32_t numel, int64_t n_rows,
+    int64_t tid, int64_t nthreads, bool fill, float fill_f) {
+  const int64_t total = n_rows * numel;
+  for (int64_t i = tid; i < total; i += nthreads) {
+    const int64_t row = i / numel;
+    const int64_t e = i - row * numel;
+    const S x = reinterpret_cast<const S*>(src + row * src_stride)[e];
+    D* dp = reinterpret_cast<D*>(dst + row * dst_stride);
+    if (aff != nullptr)
+      dp[e] = cast_elem<float, D>(
+          affine_f32((double)x, aff[e], fill, fill_f));
+    else
+      dp[e] = cast_elem<S, D>(x);
+  }
+}
+
+// One launch over the whole block: blockIdx.y picks the column, as in the
+// unpack kernels; the extra y == num_cols pass (launched only when the
+// narrow row has padding) zeroes the padding bytes.
+__global__ void narrow_rows_kernel(
+    const uint8_t* __restrict__ src,
+    int64_t src_stride,
+    uint8_t* __restrict__ dst,
+    int64_t dst_stride,
+    NarrowTable table,
+    const double2* __restrict__ aff_table,
+    int32_t num_cols,
+    int64_t n_rows,
+    int32_t has_fill,
+    float fill_f,
+    int32_t pad_off) {  // first padding byte of a narrow row
+  const int32_t c = blockIdx.y;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  if (c >= num_cols) {
+    const int32_t pad = (int32_t)dst_stride - pad_off;
+    const int64_t total = n_rows * pad;
+    for (int64_t i = tid; i < total; i += nthreads) {
+      const int64_t row = i / pad;
+      dst[row * dst_stride + pad_off + (i - row * pad)] = 0;
+    }
+    return;
+  }
+  const NarrowCol d = table.cols[c];
+  const uint8_t* sp = src + d.src_off;
+  uint8_t* dp = dst + d.dst_off;
+  if (d.src_dtype == d.dst_dtype && d.aff_base < 0) {
+    // The dtype does not change: a byte copy.
+    copy_col(sp, src_stride, nullptr, dp, dst_stride,
+             d.numel * dtype_size(d.src_dtype), n_rows, tid, nthreads);
+    return;
+  }
+  const double2* aff = d.aff_base < 0 ? nullptr : aff_table + d.aff_base;
+  const bool fill = has_fill != 0;
+  // Alignment of element 0 in row 0 of either side; both strides are
+  // multiples of 16, so it holds for every row.
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(sp);
+  const uintptr_t da = reinterpret_cast<uintptr_t>(dp);
+  const bool vec_src = (d.src_dtype == DT_F64 || d.src_dtype == DT_F32) &&
+                       (d.numel & 3) == 0 && (sa & 7) == 0;
+  const bool wide = (sa & 15) == 0;
+  if (vec_src && d.dst_dtype == DT_BF16 && (da & 7) == 0) {
+    if (d.src_dtype == DT_F64)
+      narrow_vec4<double, __hip_bfloat16>(sp, src_stride, dp, dst_stride, aff,
+                                          d.numel, n_rows, tid, nthreads,
+                                          fill, fill_f, wide);
+    else
+      narrow_vec4<float, __hip_bfloat16>(sp, src_stride, dp, dst_stride, aff,
+                                         d.numel, n_rows, tid, nthreads,
+                                         fill, fill_f, wide);
+    return;
+  }
+  if (vec_src && d.dst_dtype == DT_F32 && (da & 15) == 0) {
+    if (d.src_dtype == DT_F64)
+      narrow_vec4<double, float>(sp, src_stride, dp, dst_stride, aff,
+                                 d.numel, n_rows, tid, nthreads, fill,
+                                 fill_f, wide);
+    else
+      narrow_vec4<float, float>(sp, src_stride, dp, dst_stride, aff, d.numel,
+                                n_rows, tid, nthreads, fill, fill_f, wide);
+    return;
+  }
+  RSDL_DISPATCH_PAIR(
+      d.src_dtype, d.dst_dtype,
+      (narrow_col_loop<S, D>(sp, src_stride, dp, dst_stride, aff, d.numel,
+                             n_rows, tid, nthreads, fill, fill_f)));
+}
+
+void launch_narrow_rows(
+    const void* src, int64_t src_stride, void* dst, int64_t dst_stride,
+    const NarrowTable& table, const void* aff_table, int32_t num_cols,
+    int64_t n_rows, int32_t has_fill, float fill_f, int32_t pad_off,
+    hipStream_t stream) {
+  const int threads = 256;
+  int64_t bx = (n_rows + threads - 1) / threads;
+  if (bx > 4096) bx = 4096;
+  if (bx < 1) bx = 1;
+  dim3 grid((uint32_t)bx,
+            (uint32_t)(num_cols + (pad_off < dst_stride ? 1 : 0)));
+  hipLaunchKernelGGL(narrow_rows_kernel, grid, dim3(threads), 0, stream,
+                     reinterpret_cast<const uint8_t*>(src), src_stride,
+                     reinterpret_cast<uint8_t*>(dst), dst_stride, table,
+                     reinterpret_cast<const double2*>(aff_table), num_cols,
+                     n_rows, has_fill, fill_f, pad_off);
+}
+
+void launch_unpack_rows_sweep(
+    const void* packed, int64_t row_stride, const int64_t* perm,
+    const SweepTable& table, int32_t num_cols, int32_t lanes_per_row,
+    int64_t n_rows, hipStream_t stream) {
+  const int64_t total = n_rows * lanes_per_row;
+  const int threads = 256;
+  int64_t blocks = (total + threads - 1) / threads;
+  if (blocks > 65535 * 16) blocks = 65535 * 16;  // grid-stride covers rest
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(unpack_rows_sweep_kernel, dim3((uint32_t)blocks),
+                     dim3(threads), 0, stream,
+                     reinterpret_cast<const uint2*>(packed), row_stride / 8,
+                     perm, table, num_cols, lanes_per_row, n_rows);
 }
 
 void launch_column_stats(

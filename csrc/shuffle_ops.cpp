@@ -84,6 +84,38 @@ void launch_unpack_permute_affine(const void* packed, int64_t row_stride,
                                   const void* aff_table, int32_t num_cols,
                                   int64_t n_rows, int32_t has_fill,
                                   float fill_f, hipStream_t stream);
+struct NarrowCol {
+  int32_t src_off;
+  int32_t dst_off;
+  int32_t src_dtype;
+  int32_t dst_dtype;
+  int32_t numel;
+  int32_t aff_base;
+};
+
+struct NarrowTable {
+  NarrowCol cols[128];
+};
+
+struct SweepCol {
+  int64_t col_ptr;
+  int32_t lane0;
+  int32_t lanes;
+};
+
+struct SweepTable {
+  SweepCol cols[8];
+};
+
+void launch_narrow_rows(const void* src, int64_t src_stride, void* dst,
+                        int64_t dst_stride, const NarrowTable& table,
+                        const void* aff_table, int32_t num_cols,
+                        int64_t n_rows, int32_t has_fill, float fill_f,
+                        int32_t pad_off, hipStream_t stream);
+void launch_unpack_rows_sweep(const void* packed, int64_t row_stride,
+                              const int64_t* perm, const SweepTable& table,
+                              int32_t num_cols, int32_t lanes_per_row,
+                              int64_t n_rows, hipStream_t stream);
 void launch_partition_hist(const int32_t* dest, int32_t* block_counts,
                            int64_t n, int32_t num_dests, int32_t num_blocks,
                            hipStream_t stream);
@@ -296,6 +328,158 @@ void unpack_permute_affine(const at::Tensor& packed,
       aff_table.data_ptr(), (int32_t)outs.size(), n_rows,
       nan_fill.has_value() ? 1 : 0,
       nan_fill.has_value() ? (float)*nan_fill : 0.0f, current_stream());
+}
+
+int64_t any_elem_bytes(int64_t code) {
+  switch (code) {
+    case DT_F64: case DT_I64: return 8;
+    case DT_F32: case DT_I32: return 4;
+    case DT_F16: case DT_BF16: return 2;
+    case DT_U8: return 1;
+    default:
+      TORCH_CHECK(false, "unsupported packed dtype code ", code);
+  }
+}
+
+// The one-off narrowing pass of the source cache: wide packed rows ->
+// packed rows of the output dtypes, identity row order. Column c moves from
+// src_offsets[c] (dtype src_codes[c]) to dst_offsets[c] (dtype
+// dst_codes[c]): a byte copy when the dtype stays, else the unpack kernels'
+// cast, after the affine of aff_table[aff_base[c] + e] when aff_base[c] >=
+// 0 (nan_fill as in unpack_permute_affine). Bytes of a narrow row from
+// pad_off on are written as zero. Returns the [rows, dst_stride] block.
+at::Tensor narrow_rows(const at::Tensor& packed, int64_t dst_stride,
+                       int64_t pad_off,
+                       const std::vector<int64_t>& src_offsets,
+                       const std::vector<int64_t>& src_codes,
+                       const std::vector<int64_t>& dst_offsets,
+                       const std::vector<int64_t>& dst_codes,
+                       const std::vector<int64_t>& numels,
+                       const c10::optional<at::Tensor>& aff_table,
+                       const std::vector<int64_t>& aff_base,
+                       const c10::optional<double>& nan_fill) {
+  TORCH_CHECK(packed.is_cuda(), "packed must be on GPU");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.is_contiguous(),
+              "packed must be contiguous uint8 [rows, row_stride]");
+  const size_t nc = numels.size();
+  TORCH_CHECK(src_offsets.size() == nc && src_codes.size() == nc &&
+                  dst_offsets.size() == nc && dst_codes.size() == nc &&
+                  aff_base.size() == nc,
+              "descriptor length mismatch");
+  TORCH_CHECK(nc >= 1 && nc <= 128, "1..128 columns per launch");
+  const int64_t n_rows = packed.size(0);
+  const int64_t src_stride = packed.size(1);
+  TORCH_CHECK(src_stride % 16 == 0 && dst_stride > 0 && dst_stride % 16 == 0,
+              "row strides must be multiples of 16");
+  TORCH_CHECK(pad_off >= 0 && pad_off <= dst_stride,
+              "pad_off outside the narrow row");
+  int64_t aff_rows = 0;
+  if (aff_table.has_value()) {
+    TORCH_CHECK(aff_table->is_cuda() &&
+                    aff_table->scalar_type() == at::kDouble &&
+                    aff_table->is_contiguous() && aff_table->dim() == 2 &&
+                    aff_table->size(1) == 2,
+                "aff_table must be contiguous float64 [elems, 2] on GPU");
+    aff_rows = aff_table->size(0);
+  }
+  NarrowTable table{};
+  for (size_t c = 0; c < nc; ++c) {
+    const int64_t ssz = any_elem_bytes(src_codes[c]);
+    const int64_t dsz = any_elem_bytes(dst_codes[c]);
+    const bool same = src_codes[c] == dst_codes[c] && aff_base[c] < 0;
+    if (!same) {
+      // what the cast dispatch of the kernels knows
+      TORCH_CHECK(src_codes[c] == DT_F32 || src_codes[c] == DT_F64 ||
+                      src_codes[c] == DT_I32 || src_codes[c] == DT_I64,
+                  "column ", c, ": unsupported source dtype for a cast");
+      TORCH_CHECK(dst_codes[c] == DT_F32 || dst_codes[c] == DT_F64 ||
+                      dst_codes[c] == DT_I32 || dst_codes[c] == DT_I64 ||
+                      dst_codes[c] == DT_BF16,
+                  "column ", c, ": unsupported destination dtype for a cast");
+    }
+    TORCH_CHECK(numels[c] >= 1 && src_offsets[c] >= 0 &&
+                    src_offsets[c] % ssz == 0 &&
+                    src_offsets[c] + numels[c] * ssz <= src_stride,
+                "column ", c, " does not fit the wide row");
+    TORCH_CHECK(dst_offsets[c] >= 0 && dst_offsets[c] % dsz == 0 &&
+                    dst_offsets[c] + numels[c] * dsz <= pad_off,
+                "column ", c, " does not fit the narrow row");
+    TORCH_CHECK(aff_base[c] < 0 || aff_base[c] + numels[c] <= aff_rows,
+                "affine table too short for column ", c);
+    table.cols[c] = NarrowCol{
+        (int32_t)src_offsets[c], (int32_t)dst_offsets[c],
+        (int32_t)src_codes[c],   (int32_t)dst_codes[c],
+        (int32_t)numels[c],      aff_base[c] < 0 ? -1 : (int32_t)aff_base[c],
+    };
+  }
+  auto out = at::empty({n_rows, dst_stride}, packed.options());
+  if (n_rows == 0) return out;
+  launch_narrow_rows(packed.data_ptr(), src_stride, out.data_ptr(),
+                     dst_stride, table,
+                     aff_table.has_value() ? aff_table->data_ptr() : nullptr,
+                     (int32_t)nc, n_rows, nan_fill.has_value() ? 1 : 0,
+                     nan_fill.has_value() ? (float)*nan_fill : 0.0f,
+                     (int32_t)pad_off, current_stream());
+  return out;
+}
+
+// unpack_permute for a block whose columns all keep their dtype and are
+// made of whole 8-B lanes (at most 8 columns): one row-major sweep instead
+// of one grid pass per column. Same outputs as unpack_permute.
+void unpack_permute_sweep(const at::Tensor& packed,
+                          const c10::optional<at::Tensor>& perm,
+                          const std::vector<at::Tensor>& outs,
+                          const std::vector<int64_t>& packed_offsets,
+                          const std::vector<int64_t>& src_dtype_codes) {
+  TORCH_CHECK(packed.is_cuda(), "packed must be on GPU");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.is_contiguous(),
+              "packed must be contiguous uint8 [rows, row_stride]");
+  TORCH_CHECK(outs.size() == packed_offsets.size() &&
+                  outs.size() == src_dtype_codes.size(),
+              "descriptor length mismatch");
+  TORCH_CHECK(outs.size() >= 1 && outs.size() <= 8,
+              "1..8 columns per sweep");
+  const int64_t stride = packed.size(1);
+  TORCH_CHECK(stride % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(packed.data_ptr()) % 8 == 0,
+              "packed rows must be 8-B aligned");
+  int64_t n_rows;
+  const int64_t* perm_ptr = nullptr;
+  if (perm.has_value()) {
+    TORCH_CHECK(perm->is_cuda() && perm->scalar_type() == at::kLong &&
+                    perm->is_contiguous(),
+                "perm must be contiguous int64 on GPU");
+    n_rows = perm->numel();
+    perm_ptr = perm->data_ptr<int64_t>();
+  } else {
+    n_rows = packed.size(0);
+  }
+  if (n_rows == 0) return;
+  SweepTable table{};
+  int64_t lanes_per_row = 0;
+  for (size_t c = 0; c < outs.size(); ++c) {
+    const auto& o = outs[c];
+    TORCH_CHECK(o.is_cuda() && o.is_contiguous(),
+                "output column must be contiguous GPU tensor");
+    TORCH_CHECK(o.size(0) == n_rows, "output rows mismatch");
+    TORCH_CHECK(dtype_code(o.scalar_type()) == src_dtype_codes[c],
+                "sweep: column ", c, " changes dtype");
+    const int64_t bytes =
+        o.numel() / n_rows * any_elem_bytes(src_dtype_codes[c]);
+    TORCH_CHECK(packed_offsets[c] >= 0 && packed_offsets[c] % 8 == 0 &&
+                    bytes % 8 == 0 && packed_offsets[c] + bytes <= stride &&
+                    reinterpret_cast<uintptr_t>(o.data_ptr()) % 8 == 0,
+                "sweep: column ", c, " is not made of whole 8-B lanes");
+    table.cols[c] = SweepCol{reinterpret_cast<int64_t>(o.data_ptr()),
+                             (int32_t)(packed_offsets[c] / 8),
+                             (int32_t)(bytes / 8)};
+    lanes_per_row = std::max(lanes_per_row, (packed_offsets[c] + bytes) / 8);
+  }
+  launch_unpack_rows_sweep(packed.data_ptr(), stride, perm_ptr, table,
+                           (int32_t)outs.size(), (int32_t)lanes_per_row,
+                           n_rows, current_stream());
 }
 
 // One read-only pass over a packed block: per element of the listed columns
@@ -1473,6 +1657,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("packed_offsets"), py::arg("src_dtype_codes"),
         py::arg("aff_table"), py::arg("aff_base"),
         py::arg("nan_fill") = c10::nullopt);
+  m.def("narrow_rows", &rsdl::narrow_rows, py::arg("packed"),
+        py::arg("dst_stride"), py::arg("pad_off"), py::arg("src_offsets"),
+        py::arg("src_dtype_codes"), py::arg("dst_offsets"),
+        py::arg("dst_dtype_codes"), py::arg("numels"),
+        py::arg("aff_table") = c10::nullopt,
+        py::arg("aff_base") = std::vector<int64_t>(),
+        py::arg("nan_fill") = c10::nullopt);
+  m.def("unpack_permute_sweep", &rsdl::unpack_permute_sweep,
+        py::arg("packed"), py::arg("perm"), py::arg("outs"),
+        py::arg("packed_offsets"), py::arg("src_dtype_codes"));
   m.def("column_stats", &rsdl::column_stats, py::arg("packed"),
         py::arg("packed_offsets"), py::arg("src_dtype_codes"),
         py::arg("numels"));

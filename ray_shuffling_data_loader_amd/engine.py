@@ -59,6 +59,9 @@ from ray_shuffling_data_loader_amd.ops.shuffle_ops import (
     gather_rows,
     make_affine_table,
     merge_column_stats,
+    narrow_rows,
+    narrow_schema,
+    narrow_supported,
     partition_rows,
     stats_to_affine,
     unpack_permute,
@@ -195,6 +198,17 @@ class ShuffleEngine:
             self._gen = torch.Generator()
 
         self._cached_source: Optional[torch.Tensor] = None
+        # Narrowed source cache (RSDL_NARROW_CACHE, read once here; "0" keeps
+        # the block exactly as read): the cached block is converted ONCE to
+        # the output dtypes, standardization included, so the per-epoch
+        # unpack is a plain copy of a quarter of the bytes. Set by the first
+        # _get_source when _narrow_plan() allows it.
+        self._narrow_on = os.environ.get("RSDL_NARROW_CACHE", "1") != "0"
+        # RSDL_NARROW_SWEEP=1: unpack the narrow block in one row-major
+        # sweep instead of one grid pass per column (measured slower at the
+        # flagship row, profiles/PERF.md round 10; kept for A/B runs).
+        self._narrow_sweep = os.environ.get("RSDL_NARROW_SWEEP", "0") == "1"
+        self._narrow_schema: Optional[Schema] = None
         self._stream = (
             torch.cuda.Stream(device=self.device)
             if self.device.type == "cuda"
@@ -384,6 +398,26 @@ class ShuffleEngine:
             # First read: fit once, before the first partition is built.
             # Later re-reads (source_cache="none") keep the frozen fit.
             self._fit(src)
+        plan = self._narrow_plan()
+        if plan is not None:
+            # After the fit (it reads the wide block), before the first
+            # partition: the wide block's last reference goes here, and its
+            # memory goes back to the device rather than staying reserved.
+            src = narrow_rows(
+                src,
+                self.out_schema,
+                plan,
+                affine=self._affine,
+                nan_fill=self.nan_fill,
+            )
+            self._narrow_schema = plan
+            if src.device.type == "cuda":
+                torch.cuda.current_stream(src.device).synchronize()
+                torch.cuda.empty_cache()
+            _vlog(
+                f"rank {self.rank}: narrowed the source block "
+                f"{self.base_schema.row_stride} -> {plan.row_stride} B/row"
+            )
         if self.source_cache in ("auto", "device"):
             self._cached_source = src
         elif self.source_cache == "host":
@@ -398,6 +432,41 @@ class ShuffleEngine:
             else:
                 self._cached_source = src
         return src
+
+    def _use_views(self) -> bool:
+        # Output dtype casts (e.g. fp32 -> bf16 features) happen inside the
+        # fused unpack kernel, which requires the columns path.
+        # Standardization happens in the same kernel, so it too needs the
+        # columns path.
+        hom = homogeneous_dtype(self.out_schema)
+        return (
+            not self.out_dtypes
+            and self.normalize is None
+            and (
+                self.output == "views"
+                or (self.output == "auto" and hom is not None)
+            )
+        )
+
+    def _narrow_plan(self) -> Optional[Schema]:
+        """The narrow layout the cached block is converted to, or None where
+        today's wide cache stays: the knob is off, the views path is in
+        use, the source is not cached, a column's dtype pair is not
+        supported, or the narrow row would be no smaller."""
+        if (
+            not self._narrow_on
+            or self._narrow_schema is not None
+            or self.source_cache not in ("auto", "device", "host")
+            or self._use_views()
+        ):
+            return None
+        plan = narrow_schema(self.out_schema, self.out_dtypes)
+        aff = tuple(self._affine.entries) if self._affine is not None else ()
+        if not narrow_supported(self.out_schema, plan, aff):
+            return None
+        if plan.row_stride >= self.base_schema.row_stride:
+            return None
+        return plan
 
     # ----- epoch pipeline -----------------------------------------------------
 
@@ -420,20 +489,19 @@ class ShuffleEngine:
     ) -> RowBlock:
         """One reducer partition: fused gather-permute (+ cast/pack) of the
         selected rows into a RowBlock."""
+        if self._narrow_schema is not None:
+            # The cached block already holds the output dtypes (and the
+            # standardized values): a plain same-dtype unpack.
+            cols = unpack_permute(
+                rows,
+                self._narrow_schema,
+                perm=idx.to(torch.long),
+                row_sweep=self._narrow_sweep,
+            )
+            return RowBlock(cols)
         schema = self.out_schema
         hom = homogeneous_dtype(schema)
-        # Output dtype casts (e.g. fp32 -> bf16 features) happen inside the
-        # fused unpack kernel, which requires the columns path.
-        # Standardization happens in the same kernel, so it too needs the
-        # columns path.
-        use_views = (
-            not self.out_dtypes
-            and self.normalize is None
-            and (
-                self.output == "views"
-                or (self.output == "auto" and hom is not None)
-            )
-        )
+        use_views = self._use_views()
         if use_views and hom is not None:
             esz = dtype_bytes(hom)
             gathered = gather_rows(rows, idx)

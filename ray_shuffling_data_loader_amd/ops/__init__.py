@@ -1,5 +1,7 @@
 from ray_shuffling_data_loader_amd.ops.shuffle_ops import (  # noqa: F401
     gather_rows,
+    narrow_rows,
+    narrow_schema,
     pack_columns,
     partition_rows,
     relu_mask_words,

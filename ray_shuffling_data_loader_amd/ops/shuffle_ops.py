@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from ray_shuffling_data_loader_amd.utils.schema import (
+    ColumnSpec,
     Schema,
     TORCH_TO_NUMPY_DTYPE,
 )
@@ -205,6 +206,47 @@ def make_affine_table(
     return AffineTable(entries, base, table)
 
 
+def _np_storage_dtype(dtype: torch.dtype):
+    """The numpy dtype a packed column is viewed as on the CPU paths. numpy
+    has no bfloat16, so such a column moves as int16 (and is re-viewed)."""
+    if dtype == torch.bfloat16:
+        return np.dtype(np.int16)
+    return TORCH_TO_NUMPY_DTYPE[dtype]
+
+
+def _f64_to_bf16(t: torch.Tensor) -> torch.Tensor:
+    """float64 -> bfloat16 in ONE rounding (nearest even), which is what the
+    kernels' plain cast does (cast_elem<double, bf16> in
+    csrc/shuffle_kernels.hip). torch's own ``.to(torch.bfloat16)`` rounds to
+    float32 first and so differs wherever that float32 is a bf16 tie (about
+    2^-17 of random inputs). Here the float32 step rounds to odd instead,
+    after which the second rounding cannot go wrong."""
+    f = t.float()
+    back = f.double()
+    fi = f.view(torch.int32)
+    inexact = (back != t) & ~torch.isnan(t)
+    even = (fi & 1) == 0
+    one = torch.ones((), dtype=torch.int32)
+    # toward the side the double lies on; for either sign the bit pattern
+    # grows with the magnitude
+    step = torch.where(t.abs() > back.abs(), one, -one)
+    fi = torch.where(inexact & even, fi + step, fi)
+    return fi.view(torch.float32).to(torch.bfloat16)
+
+
+_SWEEP_MAX_COLS = 8  # RSDL_SWEEP_MAX_COLS in csrc/shuffle_kernels.hip
+
+
+def row_sweep_ok(schema: Schema) -> bool:
+    """Whether a same-dtype unpack of ``schema`` can run as one row-major
+    sweep (``unpack_permute_sweep``): at most 8 columns, each made of whole
+    8-B lanes of the packed row."""
+    return 1 <= len(schema.columns) <= _SWEEP_MAX_COLS and all(
+        schema.offsets[c.name] % 8 == 0 and c.row_bytes % 8 == 0
+        for c in schema.columns
+    )
+
+
 def unpack_permute(
     packed: torch.Tensor,
     schema: Schema,
@@ -214,6 +256,7 @@ def unpack_permute(
         None, AffineTable, Dict[str, Tuple[torch.Tensor, torch.Tensor]]
     ] = None,
     nan_fill: Optional[float] = None,
+    row_sweep: bool = False,
 ) -> Dict[str, torch.Tensor]:
     """Fused gather-permute + per-column cast + pack into contiguous torch
     column tensors: out[name][i] = cast(packed[perm[i], off_name]).
@@ -228,7 +271,13 @@ def unpack_permute(
     fp64 BEFORE the narrowing cast, in the same kernel pass. With
     ``nan_fill``, a NaN source element of such a column becomes
     ``cast((float)nan_fill)``. Columns not named come out exactly as without
-    the keyword; ``affine=None`` launches the plain kernel."""
+    the keyword; ``affine=None`` launches the plain kernel.
+
+    A column whose dtype does not change is a byte copy, whatever the dtype
+    (bf16/f16 columns of a block narrowed by :func:`narrow_rows` included).
+    ``row_sweep`` (GPU) asks for the one-pass row-major kernel where no
+    column changes dtype and :func:`row_sweep_ok` holds; the outputs are the
+    same."""
     out_dtypes = out_dtypes or {}
     n = perm.numel() if perm is not None else packed.shape[0]
     if affine is not None and not isinstance(affine, AffineTable):
@@ -248,6 +297,16 @@ def unpack_permute(
             codes.append(_dtype_code(spec.dtype))
             result[spec.name] = o
         if affine is None:
+            if (
+                row_sweep
+                and row_sweep_ok(schema)
+                and all(
+                    o.dtype == spec.dtype
+                    for o, spec in zip(outs, schema.columns)
+                )
+            ):
+                hip.unpack_permute_sweep(packed, perm, outs, offs, codes)
+                return result
             hip.unpack_permute(packed, perm, outs, offs, codes)
             return result
         table = affine.table
@@ -264,12 +323,14 @@ def unpack_permute(
     perm_np = perm.cpu().numpy() if perm is not None else None
     result = {}
     for spec in schema.columns:
-        np_dt = TORCH_TO_NUMPY_DTYPE[spec.dtype]
+        np_dt = _np_storage_dtype(spec.dtype)
         view = _np_strided_view(packed_np, schema, spec.name, spec.numel, np_dt)
         arr = view[perm_np] if perm_np is not None else np.ascontiguousarray(
             view
         )
         t = torch.from_numpy(arr)
+        if t.dtype != spec.dtype:  # bf16 moved as int16
+            t = t.view(spec.dtype)
         dst_dt = out_dtypes.get(spec.name, spec.dtype)
         if affine is not None and spec.name in affine.entries:
             # The bit-exact oracle of the affine kernel: fp64 subtract, fp64
@@ -286,11 +347,130 @@ def unpack_permute(
                 )
             t = y.to(dst_dt)
         elif dst_dt != spec.dtype:
-            t = t.to(dst_dt)
+            if spec.dtype == torch.float64 and dst_dt == torch.bfloat16:
+                t = _f64_to_bf16(t)
+            else:
+                t = t.to(dst_dt)
         if spec.numel == 1:
             t = t.reshape(n)
         result[spec.name] = t
     return result
+
+
+# ---------------------------------------------------------------------------
+# Narrowed source block: the unpack's cast (and affine) done once.
+# ---------------------------------------------------------------------------
+
+# What the cast dispatch of the unpack kernels knows (csrc/shuffle_kernels.hip
+# RSDL_DISPATCH_PAIR); a column that keeps its dtype is a byte copy.
+_CAST_SRC_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+_CAST_DST_DTYPES = _CAST_SRC_DTYPES + (torch.bfloat16,)
+
+
+def narrow_schema(
+    schema: Schema, out_dtypes: Optional[Dict[str, torch.dtype]] = None
+) -> Schema:
+    """The packed layout of ``schema``'s columns at their OUTPUT dtypes:
+    same names, order and numel; the usual descending-size packing and 16-B
+    stride rule apply."""
+    out_dtypes = out_dtypes or {}
+    return Schema(
+        [
+            ColumnSpec(c.name, out_dtypes.get(c.name, c.dtype), c.numel)
+            for c in schema.columns
+        ]
+    )
+
+
+def narrow_supported(
+    schema: Schema, narrow: Schema, affine_names: Sequence[str] = ()
+) -> bool:
+    """Whether :func:`narrow_rows` can produce every column of ``narrow``
+    from ``schema``: the dtype stays (a copy), or the pair is one the cast
+    kernels know. A standardized column always goes through the cast."""
+    for spec in schema.columns:
+        dst = narrow.col(spec.name).dtype
+        if spec.dtype == dst and spec.name not in affine_names:
+            continue
+        if spec.dtype not in _CAST_SRC_DTYPES or dst not in _CAST_DST_DTYPES:
+            return False
+    return True
+
+
+def narrow_rows(
+    packed: torch.Tensor,
+    schema: Schema,
+    narrow: Schema,
+    affine: Union[
+        None, AffineTable, Dict[str, Tuple[torch.Tensor, torch.Tensor]]
+    ] = None,
+    nan_fill: Optional[float] = None,
+) -> torch.Tensor:
+    """Wide packed rows -> packed rows of ``narrow`` (see
+    :func:`narrow_schema`), identity row order, padding bytes zero.
+
+    Per column this is exactly what :func:`unpack_permute` does with
+    ``out_dtypes`` / ``affine`` / ``nan_fill``, so for any ``perm``
+
+        unpack_permute(narrow_rows(packed, ...), narrow, perm)
+        == unpack_permute(packed, schema, perm, out_dtypes, affine, nan_fill)
+
+    bit for bit: the per-element cast commutes with the row gather. GPU: one
+    launch of ``narrow_rows_kernel``. CPU: the numpy mirror built on the CPU
+    path of :func:`unpack_permute` (the oracle)."""
+    if affine is not None and not isinstance(affine, AffineTable):
+        affine = make_affine_table(affine, schema, packed.device)
+    if affine is not None and not affine.entries:
+        affine = None
+    aff_names = tuple(affine.entries) if affine is not None else ()
+    if [c.name for c in narrow.columns] != schema.names:
+        raise ValueError("narrow schema must list the same columns")
+    if not narrow_supported(schema, narrow, aff_names):
+        raise TypeError("narrow_rows: unsupported column dtype pair")
+    n = packed.shape[0]
+    if packed.is_cuda:
+        hip = _load_hip()
+        table = None
+        if affine is not None:
+            table = affine.table
+            if table is None or table.device != packed.device:
+                table = make_affine_table(
+                    affine.entries, schema, packed.device
+                ).table
+        return hip.narrow_rows(
+            packed,
+            narrow.row_stride,
+            narrow.payload_bytes,
+            [schema.offsets[c.name] for c in schema.columns],
+            [_dtype_code(c.dtype) for c in schema.columns],
+            [narrow.offsets[c.name] for c in schema.columns],
+            [_dtype_code(narrow.col(c.name).dtype) for c in schema.columns],
+            [c.numel for c in schema.columns],
+            table,
+            [
+                affine.base.get(c.name, -1) if affine is not None else -1
+                for c in schema.columns
+            ],
+            nan_fill,
+        )
+    cols = unpack_permute(
+        packed,
+        schema,
+        None,
+        out_dtypes={c.name: c.dtype for c in narrow.columns},
+        affine=affine,
+        nan_fill=nan_fill,
+    )
+    out = torch.zeros(n, narrow.row_stride, dtype=torch.uint8)
+    out_np = out.numpy()
+    for spec in narrow.columns:
+        np_dt = _np_storage_dtype(spec.dtype)
+        view = _np_strided_view(out_np, narrow, spec.name, spec.numel, np_dt)
+        t = cols[spec.name].reshape(n, spec.numel).contiguous()
+        if spec.dtype == torch.bfloat16:
+            t = t.view(torch.int16)
+        view[:] = t.numpy()
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -122,12 +122,108 @@ def normalize_bench(dev):
         )
 
 
+def narrow_bench(dev):
+    """The narrowed source cache at the flagship shard shape (RSDL_MB_ROWS
+    rows, default 12.5e6, of 100 f64 features + f64 label -> bf16): the
+    per-epoch unpack of the wide block (what RSDL_NARROW_CACHE=0 runs), the
+    one-off narrowing pass, and the per-epoch unpack of the narrow block,
+    one grid pass per column and as one row-major sweep. Rates count the
+    payload bytes read plus the bytes written."""
+    from ray_shuffling_data_loader_amd.ops import shuffle_ops
+
+    n = int(float(os.environ.get("RSDL_MB_ROWS", "12.5e6")))
+    schema = Schema(
+        [
+            ColumnSpec("features", torch.float64, 100),
+            ColumnSpec("labels", torch.float64, 1),
+        ]
+    )
+    out_dtypes = {"features": torch.bfloat16}
+    narrow = shuffle_ops.narrow_schema(schema, out_dtypes)
+    stride = schema.row_stride
+    vals = torch.empty(n, stride // 8, dtype=torch.float64, device=dev)
+    step = 1 << 20
+    for lo in range(0, n, step):  # bounded temporaries
+        vals[lo : lo + step].normal_(mean=1e6, std=3.0)
+    packed = vals.view(torch.uint8)
+    perm = torch.randperm(n, device=dev)
+    print(
+        f"narrow bench: {n} rows, wide {stride} B = {n * stride / 1e9:.2f} "
+        f"GB, narrow {narrow.row_stride} B = "
+        f"{n * narrow.row_stride / 1e9:.2f} GB"
+    )
+
+    def report(label, fn, moved):
+        ms, lo_, hi_ = median_ms(fn)
+        print(
+            f"{label:<34}: {ms:7.3f} ms [{lo_:.3f}..{hi_:.3f}]  "
+            f"{moved / ms / 1e6:7.0f} GB/s"
+        )
+
+    wide_moved = n * (schema.payload_bytes + narrow.payload_bytes)
+    narrow_moved = n * 2 * narrow.payload_bytes
+    stats = shuffle_ops.column_stats(packed, schema, ["features"])
+    affine = shuffle_ops.make_affine_table(
+        shuffle_ops.stats_to_affine(stats), schema, dev
+    )
+    report(
+        "unpack wide  f64->bf16 (per epoch)",
+        lambda: unpack_permute(
+            packed, schema, perm=perm, out_dtypes=out_dtypes
+        ),
+        wide_moved,
+    )
+    report(
+        "unpack wide  affine    (per epoch)",
+        lambda: unpack_permute(
+            packed, schema, perm=perm, out_dtypes=out_dtypes, affine=affine
+        ),
+        wide_moved,
+    )
+    report(
+        "narrow_rows  f64->bf16 (one-off)",
+        lambda: shuffle_ops.narrow_rows(packed, schema, narrow),
+        wide_moved,
+    )
+    report(
+        "narrow_rows  affine    (one-off)",
+        lambda: shuffle_ops.narrow_rows(
+            packed, schema, narrow, affine=affine
+        ),
+        wide_moved,
+    )
+    block = shuffle_ops.narrow_rows(packed, schema, narrow)
+    del packed, vals
+    for rep in range(2):  # alternate, to see the run-to-run spread
+        report(
+            f"unpack narrow per column #{rep}",
+            lambda: unpack_permute(block, narrow, perm=perm),
+            narrow_moved,
+        )
+        report(
+            f"unpack narrow row sweep  #{rep}",
+            lambda: unpack_permute(
+                block, narrow, perm=perm, row_sweep=True
+            ),
+            narrow_moved,
+        )
+    out = torch.empty_like(block)
+    report(
+        "gather_rows narrow (same bytes)",
+        lambda: gather_rows(block, perm, out=out),
+        narrow_moved,
+    )
+
+
 def main():
     assert torch.cuda.is_available()
     dev = torch.device("cuda", 0)
     print(f"device: {torch.cuda.get_device_name(0)}")
     if os.environ.get("RSDL_MB_NORMALIZE_ONLY") == "1":
         normalize_bench(dev)
+        return
+    if os.environ.get("RSDL_MB_NARROW_ONLY") == "1":
+        narrow_bench(dev)
         return
 
     n = 2_500_000
