@@ -102,5 +102,22 @@ void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        int32_t kt_w, int32_t variant, hipStream_t stream);
 void launch_slab_reduce(const float* part, float* out, int64_t nk,
                         int64_t nslabs, hipStream_t stream);
+// The train step's three wgrads (dW1 [512,128], dW2 [256,512], dW3
+// [128,256]; the 12-fragment ring tiles) as one launch. part_i must hold
+// wgrad_grouped_nslabs(mchunks).ns[i] slabs of N*K floats; the launcher
+// returns the same counts. Needs mchunks > 0.
+struct WgradGroupedSlabs {
+  int64_t ns[3];
+};
+WgradGroupedSlabs wgrad_grouped_nslabs(int64_t mchunks);
+WgradGroupedSlabs launch_wgrad_grouped(const void* AT1, const void* BT1,
+                                       float* part1, const void* AT2,
+                                       const void* BT2, float* part2,
+                                       const void* AT3, const void* BT3,
+                                       float* part3, int64_t mchunks,
+                                       hipStream_t stream);
+// RSDL_WGRAD_GROUPED and the knobs that rule the grouped launch out,
+// latched at the first call.
+bool wgrad_grouped_default();
 
 }  // namespace rsdl

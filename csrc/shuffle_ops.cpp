@@ -1198,6 +1198,24 @@ at::Tensor run_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT,
   return part;
 }
 
+// The step's three wgrads as one grouped launch (launch_wgrad_grouped):
+// (part1, part2, part3), each [ns_i, N*K] fp32. Requires mchunks > 0.
+std::vector<at::Tensor> run_wgrad_grouped(
+    const at::Tensor& dz1t, const at::Tensor& xt, const at::Tensor& dz2t,
+    const at::Tensor& a1t, const at::Tensor& dz3t, const at::Tensor& a2t,
+    int64_t mchunks) {
+  const WgradGroupedSlabs ns = wgrad_grouped_nslabs(mchunks);
+  auto f32 = dz1t.options().dtype(at::kFloat);
+  auto p1 = at::empty({ns.ns[0], 512 * 128}, f32);
+  auto p2 = at::empty({ns.ns[1], 256 * 512}, f32);
+  auto p3 = at::empty({ns.ns[2], 128 * 256}, f32);
+  launch_wgrad_grouped(dz1t.data_ptr(), xt.data_ptr(), p1.data_ptr<float>(),
+                       dz2t.data_ptr(), a1t.data_ptr(), p2.data_ptr<float>(),
+                       dz3t.data_ptr(), a2t.data_ptr(), p3.data_ptr<float>(),
+                       mchunks, current_stream());
+  return {p1, p2, p3};
+}
+
 void check_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT, int64_t N,
                       int64_t K, int64_t mchunks, int64_t nt_w, int64_t kt_w,
                       int64_t variant) {
@@ -1268,6 +1286,23 @@ at::Tensor wgrad_frag_partials_bf16(const at::Tensor& AT,
   check_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
   TORCH_CHECK(mchunks > 0, "wgrad_frag_partials: mchunks must be positive");
   return run_wgrad_frag(AT, BT, N, K, mchunks, nt_w, kt_w, variant);
+}
+
+// The per-slab partials (part1 [ns1, 512*128], part2 [ns2, 256*512], part3
+// [ns3, 128*256]) of the train step's three wgrads run as ONE grouped
+// launch (csrc/wgrad_frag.hip, wgrad_grouped_kernel): dW1 = dz1^T x,
+// dW2 = dz2^T a1, dW3 = dz3^T a2, every input in the fragment layout of
+// wgrad_frag_bf16. Slab s of problem i covers chunks [s * cps_i,
+// min((s + 1) * cps_i, mchunks)) with cps_i = ceil(mchunks / ns_i).
+std::vector<at::Tensor> wgrad_grouped_partials_bf16(
+    const at::Tensor& dz1t, const at::Tensor& xt, const at::Tensor& dz2t,
+    const at::Tensor& a1t, const at::Tensor& dz3t, const at::Tensor& a2t,
+    int64_t mchunks) {
+  TORCH_CHECK(mchunks > 0, "wgrad_grouped_partials: mchunks must be positive");
+  check_wgrad_frag(dz1t, xt, 512, 128, mchunks, 2, 4, 0);
+  check_wgrad_frag(dz2t, a1t, 256, 512, mchunks, 1, 8, 0);
+  check_wgrad_frag(dz3t, a2t, 128, 256, mchunks, 1, 8, 0);
+  return run_wgrad_grouped(dz1t, xt, dz2t, a1t, dz3t, a2t, mchunks);
 }
 
 // ---------------------------------------------------------------------
@@ -1447,8 +1482,10 @@ std::vector<at::Tensor> step_finalize(
 }
 
 // The whole fused train step of the stock TabularMLP(100-512-256-128-1)
-// in 8 launches: prep -> x swizzle -> fwd chain -> bwd chain -> three
-// fragment wgrads into slab partials -> finalize. fp32 master
+// in 6 launches: prep -> x swizzle -> fwd chain -> bwd chain -> the three
+// fragment wgrads into slab partials as one grouped launch (three
+// launches, 8 in all, with wgrad_variant 1 or 2 or the grouped launch
+// off) -> finalize. fp32 master
 // ``weights`` [W1, W2, W3, w4] and ``biases`` [b1..b4] are read
 // directly. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4];
 // with ``outs`` the eight gradients are written into the caller's
@@ -1459,12 +1496,17 @@ std::vector<at::Tensor> fused_step_bf16(
     const std::vector<at::Tensor>& biases, bool pi16,
     const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
     int64_t loss, const c10::optional<at::Tensor>& weight,
-    double pos_weight, int64_t wgrad_variant) {
+    double pos_weight, int64_t wgrad_variant, int64_t wgrad_grouped) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fused_step", "loss");
   TORCH_CHECK(wgrad_variant >= 0 && wgrad_variant <= 2,
               "fused_step: wgrad_variant must be 0, 1 or 2, got ",
               wgrad_variant);
+  TORCH_CHECK(wgrad_grouped >= -1 && wgrad_grouped <= 1,
+              "fused_step: wgrad_grouped must be -1 (default), 0 or 1, got ",
+              wgrad_grouped);
+  TORCH_CHECK(wgrad_grouped != 1 || wgrad_variant == 0,
+              "fused_step: wgrad_grouped=1 needs wgrad_variant 0");
   const HeadWeights hw =
       head_weights("fused_step", x, weight, pos_weight, closs);
   check_x("fused_step", x);
@@ -1488,6 +1530,18 @@ std::vector<at::Tensor> fused_step_bf16(
   // launch_wgrad_frag. The small tiles have the direct kernel only, and
   // the launcher keeps them on it whatever the variant.
   const int64_t wv = wgrad_variant;  // 0 | 1 | 2, checked above
+  // At variant 0 the three wgrads are one grouped launch, unless
+  // RSDL_WGRAD_GROUPED=0 or a tuning knob of the separate launches asks
+  // for those (wgrad_grouped_default); wgrad_grouped 0 / 1 decides it for
+  // this call. Only the slab partition, so the grouping of the fp32 sums
+  // of dW1-dW3, differs between the two.
+  if (wv == 0 &&
+      (wgrad_grouped < 0 ? wgrad_grouped_default() : wgrad_grouped == 1)) {
+    auto p = run_wgrad_grouped(b.dz1t, *xt, b.dz2t, f.a1t, b.dz3t, f.a2t,
+                               mchunks);
+    return run_step_finalize(p[0], p[1], p[2], b.db_part, f.loss_part, M,
+                             outs);
+  }
   auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4, wv);
   auto p2 = run_wgrad_frag(b.dz2t, f.a1t, 256, 512, mchunks, 1, kt23, wv);
   auto p3 = run_wgrad_frag(b.dz3t, f.a2t, 128, 256, mchunks, 1, kt23, wv);
@@ -1711,7 +1765,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
         py::arg("rows") = 0, py::arg("loss") = 0,
         py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0,
-        py::arg("wgrad_variant") = 0);
+        py::arg("wgrad_variant") = 0, py::arg("wgrad_grouped") = -1);
+  m.def("wgrad_grouped_partials_bf16", &rsdl::wgrad_grouped_partials_bf16,
+        py::arg("dz1t"), py::arg("xt"), py::arg("dz2t"), py::arg("a1t"),
+        py::arg("dz3t"), py::arg("a2t"), py::arg("mchunks"));
   m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
         py::arg("Wstage"), py::arg("biases"),
         py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,

@@ -22,6 +22,8 @@
 // down; stages each chunk's unique fragments once per workgroup through
 // an LDS ring; the default for dW2 and dW3). launch_wgrad_frag picks:
 // explicit variant, then RSDL_WGRAD_LDS, then the per-shape default.
+// The train step runs its three wgrads as ONE launch of the ring body,
+// wgrad_grouped_kernel (launch_wgrad_grouped, at the end of the file).
 //
 // Direct kernel: NO LDS, no barriers — per m-chunk (16 rows) each wave loads
 // its (NT_W + KT_W) fragments directly from global (coalesced; waves of
@@ -41,7 +43,9 @@
 #include <hip/hip_bf16.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "chain.h"
 
@@ -277,29 +281,47 @@ constexpr int kLdsStageElems = 12 * 512;
 #define WL_WAIT(n) \
   asm volatile("s_waitcnt vmcnt(" #n ") lgkmcnt(0)" ::: "memory")
 
+// One wgrad problem of the ring kernels: everything wgrad_lds_body needs
+// besides the ring and the workgroup's index within the problem.
+struct WgradProblem {
+  const short* AT;
+  const short* BT;
+  float* part;  // [nslabs][N,K] fp32 partials
+  int32_t N, K;
+  int64_t mchunks;
+  int32_t nblk_n, nblk_k;  // nblk_n < 0: linear decode
+  int64_t nslabs, chunks_per_slab;
+};
+
+// The ring kernel's whole body. ``ring`` is the calling kernel's one
+// __shared__ object; ``wg`` is the workgroup's index within problem ``p``
+// (blockIdx.x less a multiple of 8, so wg & 7 is still the XCD).
 template <int NT_W, int KT_W>
-__global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
-    const short* __restrict__ AT, const short* __restrict__ BT,
-    float* __restrict__ dW,  // [nslabs][N,K] fp32 partials
-    int32_t N, int32_t K, int64_t mchunks, int32_t nblk_n, int32_t nblk_k,
-    int64_t nslabs, int64_t chunks_per_slab) {
+__device__ __forceinline__ void wgrad_lds_body(short* ring,
+                                               const WgradProblem& p,
+                                               uint32_t wg) {
   constexpr int S = kLdsStages;
   constexpr int P = S - 1;      // chunks issued ahead of the consumer
   constexpr int NA = 4 * NT_W;  // A fragments per chunk
   static_assert(NA + KT_W == 12, "a stage is 12 fragments, 3 per wave");
   static_assert(P - 1 == 4, "WL_WAIT counts below assume S == 6");
-  __shared__ __attribute__((aligned(16))) short ring[S * kLdsStageElems];
+  const short* __restrict__ AT = p.AT;
+  const short* __restrict__ BT = p.BT;
+  const int32_t N = p.N, K = p.K, nblk_k = p.nblk_k;
+  const int64_t mchunks = p.mchunks, nslabs = p.nslabs;
+  const int64_t chunks_per_slab = p.chunks_per_slab;
+  int32_t nblk_n = p.nblk_n;
 
   const int32_t NBLK = (nblk_n < 0 ? -nblk_n : nblk_n) * nblk_k;
   int64_t slab;
   int32_t blk;
   if (nblk_n < 0) {  // linear decode (A/B: RSDL_WGRAD_LINEAR)
     nblk_n = -nblk_n;
-    blk = (int32_t)(blockIdx.x % (uint32_t)NBLK);
-    slab = blockIdx.x / (uint32_t)NBLK;
+    blk = (int32_t)(wg % (uint32_t)NBLK);
+    slab = wg / (uint32_t)NBLK;
   } else {
-    const int32_t xcd = blockIdx.x & 7;
-    const int32_t g = blockIdx.x >> 3;
+    const int32_t xcd = wg & 7;
+    const int32_t g = wg >> 3;
     blk = g % NBLK;
     slab = (int64_t)(g / NBLK) * 8 + xcd;
   }
@@ -396,7 +418,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
 #undef WL_CONSUME
 
   // Epilogue: as in wgrad_frag_kernel.
-  float* part = dW + slab * (int64_t)N * K;
+  float* part = p.part + slab * (int64_t)N * K;
   #pragma unroll
   for (int nt = 0; nt < NT_W; nt++) {
     #pragma unroll
@@ -412,6 +434,49 @@ __global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
   }
 }
 #undef WL_WAIT
+
+template <int NT_W, int KT_W>
+__global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
+    const short* __restrict__ AT, const short* __restrict__ BT,
+    float* __restrict__ dW,  // [nslabs][N,K] fp32 partials
+    int32_t N, int32_t K, int64_t mchunks, int32_t nblk_n, int32_t nblk_k,
+    int64_t nslabs, int64_t chunks_per_slab) {
+  __shared__ __attribute__((aligned(16))) short
+      ring[kLdsStages * kLdsStageElems];
+  const WgradProblem p{AT,     BT,     dW,     N,
+                       K,      mchunks, nblk_n, nblk_k,
+                       nslabs, chunks_per_slab};
+  wgrad_lds_body<NT_W, KT_W>(ring, p, blockIdx.x);
+}
+
+// The three wgrads of the train step in ONE launch: workgroups
+// [0, start[1]) run dW1 with the <2,4> body, [start[1], start[2]) dW2 and
+// [start[2], grid) dW3 with the <1,8> body. Every start is a multiple of
+// 8, so each problem keeps the XCD decode of its own launch; the partials
+// of a problem are those wgrad_lds_kernel writes for the same slab
+// partition. With all three resident at once the slab counts no longer
+// have to fill the chip per problem: 512 workgroups in all keep every
+// slot busy and the partials at 512 x 128 KB.
+struct WgradGroupedArgs {
+  WgradProblem p[3];
+  uint32_t start[3];  // first workgroup of each problem; start[0] == 0
+};
+
+__global__ void __launch_bounds__(256, 2) wgrad_grouped_kernel(
+    const WgradGroupedArgs g) {
+  __shared__ __attribute__((aligned(16))) short
+      ring[kLdsStages * kLdsStageElems];
+  // Workgroup-uniform problem select, ahead of every barrier and every
+  // vector-memory operation.
+  const uint32_t b = blockIdx.x;
+  if (b < g.start[1]) {
+    wgrad_lds_body<2, 4>(ring, g.p[0], b);
+  } else {
+    const bool dw2 = b < g.start[2];
+    wgrad_lds_body<1, 8>(ring, dw2 ? g.p[1] : g.p[2],
+                         b - (dw2 ? g.start[1] : g.start[2]));
+  }
+}
 
 // out[i] = sum_s part[s][i] — the slab-partial reduction (fp32, float4).
 // 2-D grid: y splits the slab range so small outputs still fill the
@@ -644,6 +709,117 @@ void launch_wgrad_frag(const void* AT, const void* BT, float* dW, int32_t N,
                        reinterpret_cast<const short*>(BT), dW, N, K, mchunks,
                        nb_n, nblk_k, nslabs, chunks_per_slab);
   }
+}
+
+// ---------------------------------------------------------------------
+// Grouped launch of the step's three wgrads (wgrad_grouped_kernel).
+// ---------------------------------------------------------------------
+
+// Slab targets of dW1, dW2, dW3. Their workgroups (x2, x4, x1 output
+// blocks per slab: 144 + 288 + 80) sum to the 512 the chip holds at once,
+// and every workgroup gets about the same number of chunks. The default
+// is the split measured shortest at the flagship shape (profiles/PERF.md,
+// round 11); RSDL_WGRAD_GROUP_SLABS=ns1,ns2,ns3 (read once) overrides it
+// for tuning. The partition depends on mchunks and this knob only.
+#ifndef RSDL_WGRAD_GROUP_SLABS_DEFAULT
+#define RSDL_WGRAD_GROUP_SLABS_DEFAULT {72, 72, 80}
+#endif
+constexpr int64_t kGroupSlabsMax = 4096;
+
+// Whether fused_step_bf16 takes the grouped launch at wgrad_variant 0:
+// RSDL_WGRAD_GROUPED (0 or 1, read once) if set, else this default. Any of
+// the tuning knobs of the separate launches keeps the step on them.
+#ifndef RSDL_WGRAD_GROUPED_DEFAULT
+#define RSDL_WGRAD_GROUPED_DEFAULT 1
+#endif
+
+static const int64_t* grouped_targets() {
+  static const struct T {
+    int64_t v[3] = RSDL_WGRAD_GROUP_SLABS_DEFAULT;
+    T() {
+      const char* e = std::getenv("RSDL_WGRAD_GROUP_SLABS");
+      if (e == nullptr) return;
+      long long a = 0, b = 0, c = 0;
+      char tail = 0;
+      if (std::sscanf(e, "%lld,%lld,%lld%c", &a, &b, &c, &tail) != 3) return;
+      if (a < 1 || b < 1 || c < 1 || a > kGroupSlabsMax ||
+          b > kGroupSlabsMax || c > kGroupSlabsMax) {
+        return;
+      }
+      v[0] = a, v[1] = b, v[2] = c;
+    }
+  } t;
+  return t.v;
+}
+
+// The slab rule of launch_wgrad_frag: no slab is empty.
+static void grouped_slabs(int64_t target, int64_t mchunks, int64_t* nslabs,
+                          int64_t* cps) {
+  int64_t ns = target < mchunks ? target : mchunks;
+  *cps = (mchunks + ns - 1) / ns;
+  *nslabs = (mchunks + *cps - 1) / *cps;
+}
+
+WgradGroupedSlabs wgrad_grouped_nslabs(int64_t mchunks) {
+  WgradGroupedSlabs r{};
+  int64_t cps;
+  for (int i = 0; i < 3; i++) {
+    grouped_slabs(grouped_targets()[i], mchunks, &r.ns[i], &cps);
+  }
+  return r;
+}
+
+bool wgrad_grouped_default() {
+  static const bool on = [] {
+    for (const char* k : {"RSDL_WGRAD_SMALL_TILES", "RSDL_WGRAD_SCHED",
+                          "RSDL_WGRAD_LINEAR", "RSDL_WGRAD_WGS",
+                          "RSDL_WGRAD_LDS"}) {
+      if (std::getenv(k) != nullptr) return false;
+    }
+    const char* e = std::getenv("RSDL_WGRAD_GROUPED");
+    if (e != nullptr && (e[0] == '0' || e[0] == '1') && e[1] == '\0') {
+      return e[0] == '1';
+    }
+    return RSDL_WGRAD_GROUPED_DEFAULT != 0;
+  }();
+  return on;
+}
+
+WgradGroupedSlabs launch_wgrad_grouped(const void* AT1, const void* BT1,
+                                       float* part1, const void* AT2,
+                                       const void* BT2, float* part2,
+                                       const void* AT3, const void* BT3,
+                                       float* part3, int64_t mchunks,
+                                       hipStream_t stream) {
+  // dW1 [512,128] <2,4>; dW2 [256,512] <1,8>; dW3 [128,256] <1,8>
+  static const int32_t shp[3][4] = {
+      {512, 128, 2, 4}, {256, 512, 1, 8}, {128, 256, 1, 8}};
+  const void* at[3] = {AT1, AT2, AT3};
+  const void* bt[3] = {BT1, BT2, BT3};
+  float* part[3] = {part1, part2, part3};
+  WgradGroupedArgs g{};
+  WgradGroupedSlabs r{};
+  uint32_t grid = 0;
+  for (int i = 0; i < 3; i++) {
+    WgradProblem& p = g.p[i];
+    p.AT = reinterpret_cast<const short*>(at[i]);
+    p.BT = reinterpret_cast<const short*>(bt[i]);
+    p.part = part[i];
+    p.N = shp[i][0];
+    p.K = shp[i][1];
+    p.mchunks = mchunks;
+    p.nblk_n = p.N / (shp[i][2] * 128);
+    p.nblk_k = p.K / (shp[i][3] * 32);
+    grouped_slabs(grouped_targets()[i], mchunks, &p.nslabs,
+                  &p.chunks_per_slab);
+    r.ns[i] = p.nslabs;
+    g.start[i] = grid;
+    // slab count rounded up to the 8 XCDs: the surplus workgroups return
+    grid += (uint32_t)(((p.nslabs + 7) / 8) * 8 * p.nblk_n * p.nblk_k);
+  }
+  hipLaunchKernelGGL(wgrad_grouped_kernel, dim3(grid), dim3(256), 0, stream,
+                     g);
+  return r;
 }
 
 }  // namespace rsdl

@@ -59,6 +59,14 @@ _CHAIN_ROWS = int(os.environ.get("RSDL_CHAIN_ROWS", "0") or "0")
 # override via fused_step._WGRAD_VARIANT.
 _WGRAD_VARIANT = 0
 
+# Whether hip.fused_step_bf16 runs the three wgrads as one grouped launch
+# (csrc/wgrad_frag.hip, wgrad_grouped_kernel) at variant 0: None = the
+# extension's default (its RSDL_WGRAD_GROUPED latch, then the build's
+# default), True / False = on / off for this process. Only the slab
+# partition of the fp32 sums of dW1-dW3 differs. Tests may override via
+# fused_step._WGRAD_GROUPED.
+_WGRAD_GROUPED = None
+
 # Native glue (default on; RSDL_NATIVE_GLUE=0 or fused_step._NATIVE_GLUE =
 # False forces the composed path): the whole schedule runs inside one
 # extension call, hip.fused_step_bf16, with the weight staging and the
@@ -206,9 +214,12 @@ def _rows_kw() -> dict:
 
 
 def _wgrad_kw() -> dict:
-    """``wgrad_variant=`` for hip.fused_step_bf16; empty at the default,
-    as _rows_kw is."""
-    return {"wgrad_variant": _WGRAD_VARIANT} if _WGRAD_VARIANT else {}
+    """``wgrad_variant=`` / ``wgrad_grouped=`` for hip.fused_step_bf16;
+    empty at the defaults, as _rows_kw is."""
+    kw = {"wgrad_variant": _WGRAD_VARIANT} if _WGRAD_VARIANT else {}
+    if _WGRAD_GROUPED is not None:
+        kw["wgrad_grouped"] = int(bool(_WGRAD_GROUPED))
+    return kw
 
 
 def _native_ok(hip, lin, x, target, grad_hook) -> bool:

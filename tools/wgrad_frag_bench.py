@@ -8,7 +8,11 @@ partials, no zero-fill and no slab_reduce), alternating the direct
 kernel (variant 1) and the LDS-ring kernel (variant 2) in one process,
 and applies the rule a per-shape default has to pass: every ring timing
 below every direct timing, and the median difference at least three
-times the larger within-variant spread. One JSON line per shape."""
+times the larger within-variant spread. One JSON line per shape.
+
+``--grouped [ROUNDS]`` times the step's three wgrad launches against the
+one grouped launch that replaces them (wgrad_grouped_kernel), alternated
+the same way; RSDL_WGRAD_GROUP_SLABS picks the split under test."""
 import argparse
 import json
 import os
@@ -90,15 +94,72 @@ def ab(M, rounds):
         }), flush=True)
 
 
+def grouped(M, rounds):
+    """The three wgrads as the step launches them at variant 0, alone (raw
+    partials): three launches against the one grouped launch, alternated
+    in one process; the same rule as ``ab``. One JSON line."""
+    hip = _load_hip()
+    mchunks = 2 * ((M + 31) // 32)
+    ins = [inputs(N, K, mchunks) for N, K in SHAPES]
+    cfg = [_WGRAD_FRAG_CFG[s] for s in SHAPES]
+
+    def three():
+        return [hip.wgrad_frag_partials_bf16(at, bt, N, K, mchunks, nt, kt)
+                for (N, K), (at, bt), (nt, kt) in zip(SHAPES, ins, cfg)]
+
+    def one():
+        return hip.wgrad_grouped_partials_bf16(
+            ins[0][0], ins[0][1], ins[1][0], ins[1][1], ins[2][0],
+            ins[2][1], mchunks)
+
+    arms = {"three": three, "grouped": one}
+    us = {k: [] for k in arms}
+    slabs = {k: [p.shape[0] for p in fn()] for k, fn in arms.items()}
+    for r in range(-1, rounds):  # round -1: discarded warm-up pair
+        for k, fn in arms.items():
+            us_k = t(fn) * 1e3
+            if r >= 0:
+                us[k].append(us_k)
+    in_by = sum(at.numel() + bt.numel() for at, bt in ins) * 2
+    by = {k: in_by + sum(ns * N * K * 4
+                         for ns, (N, K) in zip(slabs[k], SHAPES))
+          for k in arms}
+    med = {k: statistics.median(us[k]) for k in us}
+    spread = max(max(us[k]) - min(us[k]) for k in us)
+    diff = med["three"] - med["grouped"]
+    passes = max(us["grouped"]) < min(us["three"]) and diff >= 3 * spread
+    print(json.dumps({
+        "M": M,
+        "group_slabs": os.environ.get("RSDL_WGRAD_GROUP_SLABS", "default"),
+        "three_slabs": slabs["three"], "grouped_slabs": slabs["grouped"],
+        "three_us": [round(x, 2) for x in us["three"]],
+        "grouped_us": [round(x, 2) for x in us["grouped"]],
+        "three_med_us": round(med["three"], 2),
+        "grouped_med_us": round(med["grouped"], 2),
+        "three_bytes_MB": round(by["three"] / 1e6, 1),
+        "grouped_bytes_MB": round(by["grouped"] / 1e6, 1),
+        "three_TBps": round(by["three"] / med["three"] / 1e6, 2),
+        "grouped_TBps": round(by["grouped"] / med["grouped"] / 1e6, 2),
+        "median_diff_us": round(diff, 2),
+        "max_spread_us": round(spread, 2),
+        "grouped_passes_rule": passes,
+    }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--ab", type=int, nargs="?", const=5, default=0,
+                   metavar="ROUNDS")
+    p.add_argument("--grouped", type=int, nargs="?", const=7, default=0,
                    metavar="ROUNDS")
     p.add_argument("--rows", type=int, default=250_000)
     args = p.parse_args()
     M = args.rows
     if args.ab:
         ab(M, args.ab)
+        return
+    if args.grouped:
+        grouped(M, args.grouped)
         return
     mchunks = 2 * ((M + 31) // 32)
     print(f"RSDL_WGRAD_SCHED={os.environ.get('RSDL_WGRAD_SCHED', '0')}")
