@@ -424,6 +424,23 @@ __global__ void pack_columns_kernel(
   const ColDesc d = table.cols[c];
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  // A 2-B or 1-B column (f16, bf16, u8) that keeps its dtype is outside the
+  // cast dispatch: its elements move as bit patterns, as copy_col moves
+  // them on the unpack side. The host refuses every other pair the
+  // dispatch does not know (check_col_pair in shuffle_ops.cpp).
+  if (d.src_dtype == d.dst_dtype && d.src_dtype >= DT_F16) {
+    if (dtype_size(d.src_dtype) == 2)
+      pack_col_loop<uint16_t, uint16_t>(
+          packed, row_stride, perm,
+          reinterpret_cast<const uint16_t*>(d.col_ptr), d.packed_off,
+          d.numel, n_rows, tid, nthreads);
+    else
+      pack_col_loop<uint8_t, uint8_t>(
+          packed, row_stride, perm,
+          reinterpret_cast<const uint8_t*>(d.col_ptr), d.packed_off,
+          d.numel, n_rows, tid, nthreads);
+    return;
+  }
   RSDL_DISPATCH_PAIR(
       d.dst_dtype, d.src_dtype,
       (pack_col_loop<S, D>(packed, row_stride, perm,
@@ -547,6 +564,24 @@ __global__ void pack_tiled_kernel(
     for (int32_t c = 0; c < num_cols; ++c) {
       const ColDesc d = table.cols[c];
       const int64_t elems = (int64_t)rows_here * d.numel;
+      if (d.src_dtype == d.dst_dtype && d.src_dtype >= DT_F16) {
+        // Same-dtype f16 / bf16 / u8: a bit copy (see pack_columns_kernel).
+        const bool two = dtype_size(d.src_dtype) == 2;
+        for (int64_t t = threadIdx.x; t < elems; t += blockDim.x) {
+          const int32_t r = (int32_t)(t / d.numel);
+          const int32_t e = (int32_t)(t - (int64_t)r * d.numel);
+          uint8_t* dst_base =
+              lds_tile + (int64_t)r * lds_stride + d.packed_off;
+          if (two)
+            reinterpret_cast<uint16_t*>(dst_base)[e] =
+                reinterpret_cast<const uint16_t*>(
+                    d.col_ptr)[row0 * d.numel + t];
+          else
+            dst_base[e] = reinterpret_cast<const uint8_t*>(
+                d.col_ptr)[row0 * d.numel + t];
+        }
+        continue;
+      }
       for (int64_t t = threadIdx.x; t < elems; t += blockDim.x) {
         const int32_t r = (int32_t)(t / d.numel);
         const int32_t e = (int32_t)(t - (int64_t)r * d.numel);

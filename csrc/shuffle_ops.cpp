@@ -151,6 +151,39 @@ int32_t dtype_code(at::ScalarType st) {
   }
 }
 
+const char* dtype_name(int64_t code) {
+  switch (code) {
+    case DT_F32: return "float32";
+    case DT_F64: return "float64";
+    case DT_I32: return "int32";
+    case DT_I64: return "int64";
+    case DT_F16: return "float16";
+    case DT_BF16: return "bfloat16";
+    case DT_U8: return "uint8";
+    default: return "unknown";
+  }
+}
+
+// What pack_columns, pack_columns_tiled and unpack_permute can do with one
+// column: keep its dtype (a byte copy, any of the seven dtypes), or one of
+// the casts RSDL_DISPATCH_PAIR knows ({f32, f64, i32, i64} to the same four
+// or bf16). Any other pair would leave the destination unwritten, so it is
+// refused here, before the launch.
+void check_col_pair(const char* who, size_t col, int64_t from, int64_t to) {
+  TORCH_CHECK(from >= DT_F32 && from <= DT_U8 && to >= DT_F32 && to <= DT_U8,
+              who, ": column ", col, ": unknown dtype code (", from, " -> ",
+              to, ")");
+  const bool cast_src =
+      from == DT_F32 || from == DT_F64 || from == DT_I32 || from == DT_I64;
+  const bool cast_dst = to == DT_F32 || to == DT_F64 || to == DT_I32 ||
+                        to == DT_I64 || to == DT_BF16;
+  TORCH_CHECK(from == to || (cast_src && cast_dst), who, ": column ", col,
+              ": no kernel converts ", dtype_name(from), " to ",
+              dtype_name(to),
+              " (a column keeps its dtype, or goes from float32, float64, "
+              "int32 or int64 to one of those or to bfloat16)");
+}
+
 hipStream_t current_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
@@ -238,6 +271,8 @@ void unpack_permute(const at::Tensor& packed,
     TORCH_CHECK(o.is_cuda() && o.is_contiguous(),
                 "output column must be contiguous GPU tensor");
     TORCH_CHECK(o.size(0) == n_rows, "output rows mismatch");
+    check_col_pair("unpack_permute", c, src_dtype_codes[c],
+                   dtype_code(o.scalar_type()));
     table.cols[c] = ColDesc{
         reinterpret_cast<int64_t>(o.data_ptr()),
         (int32_t)packed_offsets[c],
@@ -308,6 +343,8 @@ void unpack_permute_affine(const at::Tensor& packed,
     TORCH_CHECK(o.size(0) == n_rows, "output rows mismatch");
     const int64_t numel = o.numel() / n_rows;
     const int64_t esz = src_elem_bytes(src_dtype_codes[c]);
+    check_col_pair("unpack_permute_affine", c, src_dtype_codes[c],
+                   dtype_code(o.scalar_type()));
     TORCH_CHECK(packed_offsets[c] >= 0 && packed_offsets[c] % esz == 0 &&
                     packed_offsets[c] + numel * esz <= stride,
                 "column ", c, " does not fit the packed row");
@@ -549,6 +586,9 @@ at::Tensor pack_columns(const std::vector<at::Tensor>& cols,
                         const c10::optional<at::Tensor>& perm) {
   TORCH_CHECK(!cols.empty(), "need at least one column");
   TORCH_CHECK(cols.size() <= 128, "at most 128 columns per launch");
+  TORCH_CHECK(cols.size() == packed_offsets.size() &&
+                  cols.size() == packed_dtype_codes.size(),
+              "descriptor length mismatch");
   TORCH_CHECK(row_stride % 16 == 0, "row_stride must be multiple of 16");
   int64_t n_rows = cols[0].size(0);
   const int64_t* perm_ptr = nullptr;
@@ -568,6 +608,8 @@ at::Tensor pack_columns(const std::vector<at::Tensor>& cols,
     TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
                 "input column must be contiguous GPU tensor");
     TORCH_CHECK(t.size(0) == n_rows, "column rows mismatch");
+    check_col_pair("pack_columns", c, dtype_code(t.scalar_type()),
+                   packed_dtype_codes[c]);
     table.cols[c] = ColDesc{
         reinterpret_cast<int64_t>(t.data_ptr()),
         (int32_t)packed_offsets[c],
@@ -633,6 +675,9 @@ at::Tensor pack_columns_tiled(const std::vector<at::Tensor>& cols,
                               int64_t row_stride,
                               const c10::optional<at::Tensor>& out) {
   TORCH_CHECK(!cols.empty() && cols.size() <= 128, "1..128 columns");
+  TORCH_CHECK(cols.size() == packed_offsets.size() &&
+                  cols.size() == packed_dtype_codes.size(),
+              "descriptor length mismatch");
   TORCH_CHECK(row_stride % 16 == 0, "row_stride must be multiple of 16");
   int64_t n_rows = cols[0].size(0);
   at::Tensor packed;
@@ -653,6 +698,8 @@ at::Tensor pack_columns_tiled(const std::vector<at::Tensor>& cols,
     TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
                 "input column must be contiguous GPU tensor");
     TORCH_CHECK(t.size(0) == n_rows, "column rows mismatch");
+    check_col_pair("pack_columns_tiled", c, dtype_code(t.scalar_type()),
+                   packed_dtype_codes[c]);
     table.cols[c] = ColDesc{
         reinterpret_cast<int64_t>(t.data_ptr()),
         (int32_t)packed_offsets[c],
@@ -1699,13 +1746,23 @@ void eval_accumulate(const at::Tensor& part, const at::Tensor& acc,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X (gfx950) fused shuffle kernels";
-  m.def("gather_rows", &rsdl::gather_rows, "row gather of packed rows",
+  m.def("gather_rows", &rsdl::gather_rows,
+        "dst[i, :] = src[perm[i], :] for int64 or int32 perm; rows are a "
+        "multiple of 16 B wide. Precondition, NOT checked: every index lies "
+        "in [0, src rows); an index outside reads out of bounds.",
         py::arg("src"), py::arg("perm"));
-  m.def("gather_rows_out", &rsdl::gather_rows_out, py::arg("src"),
-        py::arg("perm"), py::arg("dst"));
-  m.def("unpack_permute", &rsdl::unpack_permute, py::arg("packed"),
-        py::arg("perm"), py::arg("outs"), py::arg("packed_offsets"),
-        py::arg("src_dtype_codes"));
+  m.def("gather_rows_out", &rsdl::gather_rows_out,
+        "gather_rows into the first perm.numel() rows of dst; further rows "
+        "of dst are left alone. Same unchecked precondition on perm.",
+        py::arg("src"), py::arg("perm"), py::arg("dst"));
+  m.def("unpack_permute", &rsdl::unpack_permute,
+        "outs[c][i] = cast(column c of packed row perm[i]). Each column "
+        "keeps its dtype or takes a cast from float32/float64/int32/int64 "
+        "to one of those or bfloat16; any other pair raises before the "
+        "launch. Precondition, NOT checked: perm indices lie in [0, packed "
+        "rows); an index outside reads out of bounds.",
+        py::arg("packed"), py::arg("perm"), py::arg("outs"),
+        py::arg("packed_offsets"), py::arg("src_dtype_codes"));
   m.def("unpack_permute_affine", &rsdl::unpack_permute_affine,
         py::arg("packed"), py::arg("perm"), py::arg("outs"),
         py::arg("packed_offsets"), py::arg("src_dtype_codes"),
@@ -1724,14 +1781,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("column_stats", &rsdl::column_stats, py::arg("packed"),
         py::arg("packed_offsets"), py::arg("src_dtype_codes"),
         py::arg("numels"));
-  m.def("pack_columns", &rsdl::pack_columns, py::arg("cols"),
-        py::arg("packed_offsets"), py::arg("packed_dtype_codes"),
-        py::arg("row_stride"), py::arg("perm") = c10::nullopt);
-  m.def("pack_columns_tiled", &rsdl::pack_columns_tiled, py::arg("cols"),
-        py::arg("packed_offsets"), py::arg("packed_dtype_codes"),
-        py::arg("row_stride"), py::arg("out") = c10::nullopt);
-  m.def("partition_build_perm", &rsdl::partition_build_perm, py::arg("dest"),
-        py::arg("num_dests"));
+  m.def("pack_columns", &rsdl::pack_columns,
+        "packed[perm[i]] column c = cast(cols[c][i]) (perm None: row i). "
+        "Dtype pairs as unpack_permute, from the tensor's dtype to the "
+        "packed one; any other pair raises before the launch. Padding bytes "
+        "are not written. Precondition, NOT checked: perm is a permutation "
+        "of [0, rows); an index outside writes out of bounds.",
+        py::arg("cols"), py::arg("packed_offsets"),
+        py::arg("packed_dtype_codes"), py::arg("row_stride"),
+        py::arg("perm") = c10::nullopt);
+  m.def("pack_columns_tiled", &rsdl::pack_columns_tiled,
+        "pack_columns without perm through an LDS tile, optionally into "
+        "``out``. Same dtype pairs; padding bytes are undefined.",
+        py::arg("cols"), py::arg("packed_offsets"),
+        py::arg("packed_dtype_codes"), py::arg("row_stride"),
+        py::arg("out") = c10::nullopt);
+  m.def("partition_build_perm", &rsdl::partition_build_perm,
+        "(perm int32 [n], counts int64 [num_dests]): the gather permutation "
+        "that groups rows by destination, for int32 or int64 dest and "
+        "num_dests in [1, 1024]. Precondition, NOT checked: every id lies "
+        "in [0, num_dests); an id outside indexes LDS out of bounds.",
+        py::arg("dest"), py::arg("num_dests"));
   m.def("wgrad_bf16", &rsdl::wgrad_bf16, py::arg("dy"), py::arg("x"),
         py::arg("with_bias") = true);
   m.def("relu_bwd_bias", &rsdl::relu_bwd_bias, py::arg("dy"), py::arg("y"));

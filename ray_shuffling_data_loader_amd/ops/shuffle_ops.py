@@ -52,9 +52,27 @@ def _load_hip():
 
 _DT_CODE = None
 
+# The column dtypes the HIP pack/unpack kernels know (DType in
+# csrc/shuffle_kernels.hip). Schema also lays out int16, int8 and bool
+# columns; those exist on the CPU paths only.
+_KERNEL_DTYPES = (
+    torch.float32,
+    torch.float64,
+    torch.int32,
+    torch.int64,
+    torch.float16,
+    torch.bfloat16,
+    torch.uint8,
+)
+
 
 def _dtype_code(dtype: torch.dtype) -> int:
     global _DT_CODE
+    if dtype not in _KERNEL_DTYPES:
+        raise TypeError(
+            f"the HIP shuffle kernels have no column dtype {dtype}; they "
+            "know " + ", ".join(str(d) for d in _KERNEL_DTYPES)
+        )
     if _DT_CODE is None:
         hip = _load_hip()
         _DT_CODE = {
@@ -80,7 +98,13 @@ def gather_rows(
     out: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Row gather of a 2-D contiguous tensor. The reducer-side full row
-    permutation (reference shuffle.py:194) fused with the implicit concat."""
+    permutation (reference shuffle.py:194) fused with the implicit concat.
+
+    ``perm`` (int64 or int32) may be any selection: a subset, repeats, or
+    empty. With ``out`` (at least ``perm.numel()`` rows) the result is its
+    leading rows and the rest of ``out`` is left alone. On the GPU the
+    indices are NOT checked: one outside ``[0, len(src))`` reads out of
+    bounds."""
     if src.is_cuda:
         hip = _load_hip()
         if out is not None:
@@ -123,7 +147,14 @@ def pack_columns(
 ) -> torch.Tensor:
     """Interleave column tensors into packed rows (cast to the schema dtype
     per column). ``perm`` scatters row i of the input to row perm[i] of the
-    output."""
+    output.
+
+    GPU: a column keeps its dtype (any of float32/64, int32/64, float16,
+    bfloat16, uint8: a byte copy) or is cast from float32/64 or int32/64 to
+    one of those or to bfloat16; every other pair raises before the launch
+    (the table is in docs/PARITY.md). Padding bytes are undefined. ``perm``
+    must be a permutation of the rows: it is NOT checked, and an index
+    outside ``[0, n)`` writes out of bounds."""
     first = next(iter(columns.values()))
     n = first.shape[0]
     if first.is_cuda:
@@ -275,6 +306,11 @@ def unpack_permute(
 
     A column whose dtype does not change is a byte copy, whatever the dtype
     (bf16/f16 columns of a block narrowed by :func:`narrow_rows` included).
+    A column that does change goes from float32/64 or int32/64 to one of
+    those or to bfloat16; on the GPU every other pair raises before the
+    launch (docs/PARITY.md has the table). ``perm`` may be a subset or
+    repeat rows; on the GPU its indices are NOT checked, and one outside the
+    packed block reads out of bounds.
     ``row_sweep`` (GPU) asks for the one-pass row-major kernel where no
     column changes dtype and :func:`row_sweep_ok` holds; the outputs are the
     same."""
@@ -665,7 +701,11 @@ def partition_rows(
     permutation in two O(N) index passes (no radix sort); the row move is
     the roofline gather. Order within a destination is block-local (a full
     random permutation is applied downstream either way). CPU: stable
-    argsort (order matches the reference's boolean-mask partition)."""
+    argsort (order matches the reference's boolean-mask partition).
+
+    ``dest`` is int64 or int32 and ``num_dests`` at most 1024 on the GPU,
+    where the ids are NOT checked: one outside ``[0, num_dests)`` indexes
+    the kernels' LDS counters out of bounds."""
     if packed.is_cuda:
         hip = _load_hip()
         perm, counts = hip.partition_build_perm(dest, num_dests)

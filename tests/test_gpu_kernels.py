@@ -234,7 +234,18 @@ def test_pack_columns_tiled_matches_cpu(dev):
     n = 5000
     cols = rand_cols(n, schema)
     expected = pack_columns(cols, schema)  # CPU oracle
-    got = pack_columns({k: v.to(dev) for k, v in cols.items()}, schema).cpu()
+    # The tiled binding itself, by name: ops.pack_columns picks between it
+    # and the scatter kernel, and test_pack_columns_matches_cpu goes through
+    # that choice.
+    from ray_shuffling_data_loader_amd import _rsdl_hip
+    from ray_shuffling_data_loader_amd.ops.shuffle_ops import _dtype_code
+
+    got = _rsdl_hip.pack_columns_tiled(
+        [cols[c.name].to(dev) for c in schema.columns],
+        [schema.offsets[c.name] for c in schema.columns],
+        [_dtype_code(c.dtype) for c in schema.columns],
+        schema.row_stride,
+    ).cpu()
     for spec in schema.columns:
         off = schema.offsets[spec.name]
         nb = spec.row_bytes
