@@ -1379,10 +1379,16 @@ struct PrepOut {
 
 // ``bufs``: optional caller buffers for the six bf16 outputs. ``target``
 // fp32 passes through untouched (no launch work); fp64 is cast in-kernel.
+// ``bufs_valid``: the caller's buffers already hold the images of ``w``
+// (kept so by the update kernels), so only the target is cast, and
+// nothing is launched for an fp32 one.
 PrepOut run_step_prep(const std::vector<at::Tensor>& w,
                       const c10::optional<at::Tensor>& target,
-                      const c10::optional<std::vector<at::Tensor>>& bufs) {
+                      const c10::optional<std::vector<at::Tensor>>& bufs,
+                      bool bufs_valid = false) {
   check_master(w, "step_prep");
+  TORCH_CHECK(!bufs_valid || bufs.has_value(),
+              "step_prep: bufs_valid needs the caller's buffers");
   const int64_t numel[6] = {512 * 112, 256 * 512, 128 * 256,
                             256 * 512, 128 * 256, 128};
   at::Tensor o[6];
@@ -1405,6 +1411,7 @@ PrepOut run_step_prep(const std::vector<at::Tensor>& w,
   }
   PrepOut r{o[0], o[1], o[2], o[3], o[4], o[5], at::Tensor()};
   StepPrepArgs p{};
+  p.b0 = bufs_valid ? step_prep_target_only() : 0;
   p.W1 = w[0].data_ptr<float>();
   p.W2 = w[1].data_ptr<float>();
   p.W3 = w[2].data_ptr<float>();
@@ -1435,12 +1442,15 @@ PrepOut run_step_prep(const std::vector<at::Tensor>& w,
 }
 
 // outs (optional): [dW1, dW2, dW3, dW4, db1, db2, db3, db4] contiguous
-// fp32. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4].
+// fp32. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4]. With
+// ``opt`` (validated by make_step_opt) the launch is step_finalize_update
+// of that kind.
 std::vector<at::Tensor> run_step_finalize(
     const at::Tensor& part1, const at::Tensor& part2,
     const at::Tensor& part3, const at::Tensor& db_part,
     const at::Tensor& loss_part, int64_t M,
-    const c10::optional<std::vector<at::Tensor>>& outs) {
+    const c10::optional<std::vector<at::Tensor>>& outs,
+    const StepOptArgs* opt = nullptr, int kind = 0) {
   auto chk = [](const at::Tensor& t, int64_t w, const char* nm) {
     TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
                     t.is_contiguous() && t.dim() == 2 && t.size(1) == w &&
@@ -1503,8 +1513,95 @@ std::vector<at::Tensor> run_step_finalize(
   p.db3 = o[6].data_ptr<float>();
   p.db4 = o[7].data_ptr<float>();
   p.loss = loss.data_ptr<float>();
-  launch_step_finalize(p, current_stream());
+  if (opt != nullptr) {
+    launch_step_finalize_update(p, *opt, kind, current_stream());
+  } else {
+    launch_step_finalize(p, current_stream());
+  }
   return {loss, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
+}
+
+// Element counts in the parameter order of StepOptArgs.
+constexpr int64_t kParamNumel[8] = {512 * 100, 256 * 512, 128 * 256, 128,
+                                    512,       256,       128,       1};
+
+// One of the eight fp32 tensors of ``what`` (gradients, a state slot):
+// contiguous, the parameter's element count, on ``dev``; the three large
+// matrices are accessed as float4.
+void check_param_like(const char* who, const char* what, int64_t idx, int i,
+                      const at::Tensor& t, int dev) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == kParamNumel[i] &&
+                  t.get_device() == dev,
+              who, ": ", what, " ", idx, " must be contiguous fp32 with ",
+              kParamNumel[i], " elements on the weights' GPU");
+  TORCH_CHECK(i >= 3 || reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": ", what, " ", idx, " must be 16-byte aligned");
+}
+
+// Validated launch arguments of the update kernels (csrc/step_glue.hip).
+// ``state``: 8 momentum buffers for SGD with momentum, none without, and
+// 8 first then 8 second moments for AdamW, in parameter order. ``staged``:
+// the six bf16 buffers of step_prep. ``hyper``: the h[] of step_glue.h,
+// each rounded to fp32 here.
+StepOptArgs make_step_opt(const char* who,
+                          const std::vector<at::Tensor>& weights,
+                          const std::vector<at::Tensor>& biases,
+                          const std::vector<at::Tensor>& state,
+                          const std::vector<at::Tensor>& staged,
+                          int64_t kind, const std::vector<double>& hyper) {
+  TORCH_CHECK(kind == kOptSgd || kind == kOptAdamW, who,
+              ": kind must be OPT_SGD or OPT_ADAMW, got ", kind);
+  const size_t nh = kind == kOptSgd ? 5 : 8;
+  TORCH_CHECK(hyper.size() == nh, who, ": hyper must hold ", nh,
+              " values for this kind, got ", hyper.size());
+  check_master(weights, who);
+  const int dev = weights[0].get_device();
+  for (int i = 1; i < 4; i++) {
+    TORCH_CHECK(weights[i].get_device() == dev, who, ": weight ", i,
+                " must be on weight 0's GPU");
+  }
+  check_biases(who, biases, dev);
+  StepOptArgs a{};
+  for (size_t i = 0; i < nh; i++) a.h[i] = (float)hyper[i];
+  const size_t ns = kind == kOptAdamW ? 16 : a.h[2] != 0.f ? 8 : 0;
+  TORCH_CHECK(state.size() == ns, who, ": state must hold ", ns,
+              " tensors for this kind and momentum, got ", state.size());
+  for (size_t s = 0; s < ns; s++) {
+    const int i = (int)(s % 8);
+    check_param_like(who, "state", (int64_t)s, i, state[s], dev);
+    (s < 8 ? a.s1 : a.s2)[i] = state[s].data_ptr<float>();
+  }
+  const int64_t sn[6] = {512 * 112, 256 * 512, 128 * 256,
+                         256 * 512, 128 * 256, 128};
+  TORCH_CHECK(staged.size() == 6, who, ": need six staged buffers");
+  for (int i = 0; i < 6; i++) {
+    const at::Tensor& t = staged[i];
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                    t.is_contiguous() && t.numel() == sn[i] &&
+                    t.get_device() == dev &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                who, ": staged buffer ", i,
+                " must be contiguous aligned bf16 with ", sn[i],
+                " elements on the weights' GPU");
+    a.stg[i] = reinterpret_cast<uint16_t*>(t.data_ptr());
+  }
+  for (int i = 0; i < 4; i++) {
+    a.prm[i] = weights[i].data_ptr<float>();
+    a.prm[4 + i] = biases[i].data_ptr<float>();
+  }
+  return a;
+}
+
+// The update kernels write masters and state behind autograd's back: bump
+// the version counters (shared with the parameters the detached views
+// came from), so caches keyed on ``_version`` see the write.
+void bump_versions(const std::vector<at::Tensor>& a,
+                   const std::vector<at::Tensor>& b,
+                   const std::vector<at::Tensor>& c) {
+  for (const auto* v : {&a, &b, &c}) {
+    for (const auto& t : *v) t.unsafeGetTensorImpl()->bump_version();
+  }
 }
 
 }  // namespace
@@ -1528,6 +1625,57 @@ std::vector<at::Tensor> step_finalize(
   return run_step_finalize(part1, part2, part3, db_part, loss_part, M, outs);
 }
 
+// step_finalize, then the SGD / AdamW update of every parameter from the
+// gradient just stored, in the same launch: masters ``weights`` /
+// ``biases`` and ``state`` in place, plus the bf16 images of the new
+// weights in ``staged`` (make_step_opt). Returns what step_finalize does.
+std::vector<at::Tensor> step_finalize_update(
+    const at::Tensor& part1, const at::Tensor& part2,
+    const at::Tensor& part3, const at::Tensor& db_part,
+    const at::Tensor& loss_part, int64_t M,
+    const c10::optional<std::vector<at::Tensor>>& outs,
+    const std::vector<at::Tensor>& weights,
+    const std::vector<at::Tensor>& biases,
+    const std::vector<at::Tensor>& state,
+    const std::vector<at::Tensor>& staged, int64_t kind,
+    const std::vector<double>& hyper) {
+  const StepOptArgs a = make_step_opt("step_finalize_update", weights,
+                                      biases, state, staged, kind, hyper);
+  TORCH_CHECK(part1.is_cuda() && part1.get_device() == weights[0].get_device(),
+              "step_finalize_update: part1 must be on the weights' GPU");
+  auto r = run_step_finalize(part1, part2, part3, db_part, loss_part, M, outs,
+                             &a, (int)kind);
+  bump_versions(weights, biases, state);
+  return r;
+}
+
+// The same update from already folded gradients ``grads`` = [dW1, dW2,
+// dW3, dW4, db1..db4] (finalize -> all-reduce -> update, grad_hook steps,
+// gradients from elsewhere). One launch; outputs as step_finalize_update.
+void step_update(const std::vector<at::Tensor>& grads,
+                 const std::vector<at::Tensor>& weights,
+                 const std::vector<at::Tensor>& biases,
+                 const std::vector<at::Tensor>& state,
+                 const std::vector<at::Tensor>& staged, int64_t kind,
+                 const std::vector<double>& hyper) {
+  StepOptArgs a = make_step_opt("step_update", weights, biases, state,
+                                staged, kind, hyper);
+  TORCH_CHECK(grads.size() == 8, "step_update: need eight gradients");
+  for (int i = 0; i < 8; i++) {
+    check_param_like("step_update", "grad", i, i, grads[i],
+                     weights[0].get_device());
+    a.grad[i] = grads[i].data_ptr<float>();
+  }
+  launch_step_update(a, (int)kind, current_stream());
+  bump_versions(weights, biases, state);
+}
+
+// ``opt=`` of fused_step_bf16: (state, staged, staged_valid, kind, hyper),
+// the arguments of step_finalize_update plus whether ``staged`` already
+// holds the images of ``weights``.
+using StepOpt = std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>,
+                           bool, int64_t, std::vector<double>>;
+
 // The whole fused train step of the stock TabularMLP(100-512-256-128-1)
 // in 6 launches: prep -> x swizzle -> fwd chain -> bwd chain -> the three
 // fragment wgrads into slab partials as one grouped launch (three
@@ -1537,13 +1685,20 @@ std::vector<at::Tensor> step_finalize(
 // directly. Returns [loss, dW1, dW2, dW3, dW4, db1, db2, db3, db4];
 // with ``outs`` the eight gradients are written into the caller's
 // tensors (same order). No sync, no host read: graph-capture safe.
+//
+// With ``opt`` (StepOpt) the step also applies the optimizer: the weights
+// are staged into the caller's persistent ``staged`` buffers, by step_prep
+// only when ``staged_valid`` is false (an fp64 target is still cast), and
+// the step ends in step_finalize_update, which keeps them current.
+// Without ``opt`` the launches are exactly those above.
 std::vector<at::Tensor> fused_step_bf16(
     const at::Tensor& x, const at::Tensor& target,
     const std::vector<at::Tensor>& weights,
     const std::vector<at::Tensor>& biases, bool pi16,
     const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
     int64_t loss, const c10::optional<at::Tensor>& weight,
-    double pos_weight, int64_t wgrad_variant, int64_t wgrad_grouped) {
+    double pos_weight, int64_t wgrad_variant, int64_t wgrad_grouped,
+    const c10::optional<StepOpt>& opt) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fused_step", "loss");
   TORCH_CHECK(wgrad_variant >= 0 && wgrad_variant <= 2,
@@ -1561,7 +1716,28 @@ std::vector<at::Tensor> fused_step_bf16(
   TORCH_CHECK(M > 0, "fused_step: empty batch");
   TORCH_CHECK(target.numel() == M, "fused_step: target size mismatch");
   check_biases("fused_step", biases);
-  auto pr = run_step_prep(weights, target, c10::nullopt);
+  StepOptArgs oa{};
+  c10::optional<std::vector<at::Tensor>> stage_bufs;
+  if (opt.has_value()) {
+    oa = make_step_opt("fused_step", weights, biases, std::get<0>(*opt),
+                       std::get<1>(*opt), std::get<3>(*opt),
+                       std::get<4>(*opt));
+    TORCH_CHECK(weights[0].get_device() == x.get_device(),
+                "fused_step: weight 0 must be on x's GPU");
+    stage_bufs = std::get<1>(*opt);
+  }
+  const StepOptArgs* oap = opt.has_value() ? &oa : nullptr;
+  const int okind = opt.has_value() ? (int)std::get<3>(*opt) : 0;
+  auto finalize = [&](const at::Tensor& p1, const at::Tensor& p2,
+                      const at::Tensor& p3, const at::Tensor& db_part,
+                      const at::Tensor& loss_part) {
+    auto r = run_step_finalize(p1, p2, p3, db_part, loss_part, M, outs, oap,
+                               okind);
+    if (opt.has_value()) bump_versions(weights, biases, std::get<0>(*opt));
+    return r;
+  };
+  auto pr = run_step_prep(weights, target, stage_bufs,
+                          opt.has_value() && std::get<2>(*opt));
   const int64_t mchunks = 2 * ((M + 31) / 32);
   c10::optional<at::Tensor> xt =
       at::empty({4 * mchunks * 512}, x.options());
@@ -1586,13 +1762,12 @@ std::vector<at::Tensor> fused_step_bf16(
       (wgrad_grouped < 0 ? wgrad_grouped_default() : wgrad_grouped == 1)) {
     auto p = run_wgrad_grouped(b.dz1t, *xt, b.dz2t, f.a1t, b.dz3t, f.a2t,
                                mchunks);
-    return run_step_finalize(p[0], p[1], p[2], b.db_part, f.loss_part, M,
-                             outs);
+    return finalize(p[0], p[1], p[2], b.db_part, f.loss_part);
   }
   auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4, wv);
   auto p2 = run_wgrad_frag(b.dz2t, f.a1t, 256, 512, mchunks, 1, kt23, wv);
   auto p3 = run_wgrad_frag(b.dz3t, f.a2t, 128, 256, mchunks, 1, kt23, wv);
-  return run_step_finalize(p1, p2, p3, b.db_part, f.loss_part, M, outs);
+  return finalize(p1, p2, p3, b.db_part, f.loss_part);
 }
 
 // Forward-only evaluation of the stock TabularMLP (csrc/fwd_chain.hip,
@@ -1835,7 +2010,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pi16") = false, py::arg("outs") = c10::nullopt,
         py::arg("rows") = 0, py::arg("loss") = 0,
         py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0,
-        py::arg("wgrad_variant") = 0, py::arg("wgrad_grouped") = -1);
+        py::arg("wgrad_variant") = 0, py::arg("wgrad_grouped") = -1,
+        py::arg("opt") = c10::nullopt);
+  m.def("step_finalize_update", &rsdl::step_finalize_update,
+        py::arg("part1"), py::arg("part2"), py::arg("part3"),
+        py::arg("db_part"), py::arg("loss_part"), py::arg("M"),
+        py::arg("outs"), py::arg("weights"), py::arg("biases"),
+        py::arg("state"), py::arg("staged"), py::arg("kind"),
+        py::arg("hyper"));
+  m.def("step_update", &rsdl::step_update, py::arg("grads"),
+        py::arg("weights"), py::arg("biases"), py::arg("state"),
+        py::arg("staged"), py::arg("kind"), py::arg("hyper"));
   m.def("wgrad_grouped_partials_bf16", &rsdl::wgrad_grouped_partials_bf16,
         py::arg("dz1t"), py::arg("xt"), py::arg("dz2t"), py::arg("a1t"),
         py::arg("dz3t"), py::arg("a2t"), py::arg("mchunks"));
@@ -1851,6 +2036,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("LOSS_BCE") = (int)rsdl::kLossBce;
   // the heads take sample weights / pos_weight (weight=, pos_weight=)
   m.attr("HEAD_WEIGHTS") = 1;
+  // step_update / step_finalize_update and opt= of fused_step_bf16
+  m.attr("STEP_OPTIM") = 1;
+  m.attr("OPT_SGD") = (int)rsdl::kOptSgd;
+  m.attr("OPT_ADAMW") = (int)rsdl::kOptAdamW;
   m.attr("DT_F32") = (int)rsdl::DT_F32;
   m.attr("DT_F64") = (int)rsdl::DT_F64;
   m.attr("DT_I32") = (int)rsdl::DT_I32;

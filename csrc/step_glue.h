@@ -21,6 +21,31 @@ struct StepPrepArgs {
   const double* tgt64;  // fp64 target [M], or nullptr (no cast needed)
   float* tgt32;
   int64_t M;
+  // First block index to run: 0 = everything, step_prep_target_only() =
+  // skip the weight blocks (the caller's staged buffers are already
+  // valid) and only cast the target.
+  int32_t b0;
+};
+
+// Optimizer kinds of the update kernels and the layout of ``h``, the fp32
+// hyper-parameters. Scalars that depend on the step count are formed by
+// the caller in fp64 and rounded to fp32 once.
+//   SGD    h = {grad_scale, lr, momentum, weight_decay, nesterov (0|1)}
+//   AdamW  h = {grad_scale, c1 = 1 - lr*wd, a1 = 1 - beta1, beta2,
+//               a2 = 1 - beta2, s = lr / (1 - beta1^t),
+//               q = sqrt(1 - beta2^t), eps}
+constexpr int kOptSgd = 0;
+constexpr int kOptAdamW = 1;
+
+// Parameter order of every array below: W1, W2, W3, w4, b1, b2, b3, b4.
+struct StepOptArgs {
+  float* prm[8];         // fp32 masters, updated in place
+  float* s1[8];          // SGD momentum buffer (null when momentum == 0) /
+                         // AdamW first moment
+  float* s2[8];          // AdamW second moment (null for SGD)
+  const float* grad[8];  // folded gradients (step_update only)
+  uint16_t* stg[6];      // W1s, W2s, W3s, W2Ts, W3Ts, w4b of StepPrepArgs
+  float h[8];
 };
 
 struct StepFinArgs {
@@ -43,6 +68,13 @@ struct StepFinArgs {
 
 void launch_step_prep(const StepPrepArgs& p, hipStream_t stream);
 void launch_step_finalize(const StepFinArgs& p, hipStream_t stream);
+// step_finalize, then the optimizer update of every element where its
+// gradient was just stored (``o.grad`` is not read).
+void launch_step_finalize_update(const StepFinArgs& p, const StepOptArgs& o,
+                                 int kind, hipStream_t stream);
+// The same update from the gradients in ``o.grad``.
+void launch_step_update(const StepOptArgs& o, int kind, hipStream_t stream);
+int32_t step_prep_target_only();  // StepPrepArgs::b0 that skips the weights
 // ncol = 4: part fp32 [nrows, 4] (16-byte aligned) -> acc fp64 [5] +=
 // {M, column sums}; ncol = 5: part fp32 [nrows, 8] (columns 0..4 used) ->
 // acc fp64 [6]

@@ -84,8 +84,79 @@ def parse_args():
     p.add_argument("--pos-weight", type=float, default=None, metavar="P",
                    help="positive-class weight of --loss bce (TabularMLP "
                    "path) — the same choice as fused_step(pos_weight=)")
+    p.add_argument("--optimizer",
+                   choices=["torch", "fused-sgd", "fused-adamw"],
+                   default="torch",
+                   help="torch: autograd + DDP + torch.optim.SGD (the "
+                   "default). fused-sgd / fused-adamw (TabularMLP path, "
+                   "--num-cols 100): models.fused_step.fused_step with a "
+                   "models.fused_optim.FusedOptimizer. One process passes "
+                   "optimizer= and the update runs inside the step; more "
+                   "run fused_step -> one flat gradient all-reduce -> "
+                   "opt.step(grad_scale=1/world)")
     p.add_argument("--device", type=str, default=None)
     return p.parse_args()
+
+
+def fused_train_setup(args, model, world, device):
+    """(optimizer, flat gradient buffer or None) of --optimizer fused-*.
+    With more than one process the ranks start from rank 0's parameters
+    and every .grad is a view of one flat fp32 buffer, whose last element
+    counts the ranks that still had a batch (see fused_train_step)."""
+    from ray_shuffling_data_loader_amd.models.fused_optim import (
+        FusedOptimizer,
+    )
+
+    kind = args.optimizer.split("-")[1]
+    kw = {"momentum": 0.9} if kind == "sgd" else {}
+    opt = FusedOptimizer(model, kind, lr=args.lr, **kw)
+    if world == 1:
+        return opt, None
+    params = opt._params()  # W1, W2, W3, w4, b1..b4
+    for p in params:
+        torch.distributed.broadcast(p.data, src=0)
+    flat = torch.zeros(sum(p.numel() for p in params) + 1, device=device)
+    off = 0
+    for p in params:
+        p.grad = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    model._rsdl_flat_grads = True
+    return opt, flat
+
+
+def fused_train_step(args, model, opt, flat, world, x, target, weight):
+    """One step of --optimizer fused-*. One process: the update runs
+    inside fused_step. More: fused_step fills the flat buffer, one
+    all-reduce sums it, and step_update applies the mean gradient. The
+    flat buffer's last element is 1 on a rank with a batch."""
+    from ray_shuffling_data_loader_amd.models.fused_step import fused_step
+
+    kw = dict(loss=args.loss, sample_weight=weight,
+              pos_weight=args.pos_weight)
+    x = x.bfloat16().contiguous()
+    target = target.reshape(-1, 1)
+    if world == 1:
+        return fused_step(model, x, target, optimizer=opt, **kw)
+    loss = fused_step(model, x, target, **kw)
+    flat[-1] = 1.0
+    torch.distributed.all_reduce(flat)
+    opt.step(grad_scale=1.0 / world)
+    return loss
+
+
+def fused_train_drain(opt, flat, world):
+    """Reducer partitions are binomial, so ranks run out of batches at
+    different steps. A rank that is done keeps answering the others'
+    all-reduces with zero gradients, and applies the same update they do,
+    until one all-reduce finds no rank with a batch; the last rank to
+    finish triggers exactly that one. Only ranks that are done read the
+    count back."""
+    while True:
+        flat.zero_()
+        torch.distributed.all_reduce(flat)
+        if flat[-1].item() == 0.0:
+            return
+        opt.step(grad_scale=1.0 / world)
 
 
 def train_main(args, world, rank):
@@ -162,7 +233,13 @@ def train_main(args, world, rank):
             device=device,
         )
         model = TabularMLP(args.num_cols).to(device)
-    if world > 1:
+    fused = args.optimizer != "torch"
+    if fused and (tabular or args.num_cols != 100
+                  or args.mock_train_step_time is not None):
+        raise SystemExit("--optimizer fused-* is for the TabularMLP path "
+                         "(--spec float) at --num-cols 100 with a real "
+                         "train step")
+    if world > 1 and not fused:
         model = torch.nn.parallel.DistributedDataParallel(model)
         if args.fp16_allreduce:
             from torch.distributed.algorithms.ddp_comm_hooks import (
@@ -172,7 +249,10 @@ def train_main(args, world, rank):
             model.register_comm_hook(
                 None, default_hooks.fp16_compress_hook
             )
-    opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9)
+    if fused:
+        opt, flat = fused_train_setup(args, model, world, device)
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9)
     if args.loss == "bce" and tabular:
         raise SystemExit("--loss bce is for the TabularMLP path "
                          "(--spec float)")
@@ -213,7 +293,7 @@ def train_main(args, world, rank):
         # a sleep with the real fwd/bwd commented out).
         join_ctx = (
             model.join()
-            if world > 1 and args.mock_train_step_time is None
+            if world > 1 and args.mock_train_step_time is None and not fused
             else contextlib.nullcontext()
         )
         with join_ctx:
@@ -225,6 +305,9 @@ def train_main(args, world, rank):
                 wait_times.append(time.perf_counter() - t_wait)
                 if args.mock_train_step_time is not None:
                     time.sleep(args.mock_train_step_time)
+                elif fused:
+                    loss = fused_train_step(args, model, opt, flat, world,
+                                            data[0], target, weight)
                 else:
                     x = data if tabular else data[0]
                     opt.zero_grad(set_to_none=True)
@@ -233,6 +316,8 @@ def train_main(args, world, rank):
                     opt.step()
                 n_batches += 1
                 t_wait = time.perf_counter()
+            if fused and world > 1:
+                fused_train_drain(opt, flat, world)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         dur = time.perf_counter() - t_epoch

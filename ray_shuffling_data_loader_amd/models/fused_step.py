@@ -16,7 +16,19 @@ and no copy:
   5-7. three fragment-major wgrad kernels into per-slab partials
   8. step_finalize: all partials -> dW1 [512,100], dW2, dW3, dW4, db1..4
      and the scalar loss, fixed summation order, written in place
-then the optimizer. The composed path (FakeHip CPU mirror, grad_hook
+then the optimizer. With ``optimizer=`` (models/fused_optim.py, SGD or
+AdamW) the optimizer is part of the schedule:
+  1. step_prep only when the optimizer's staged weight buffers are not
+     valid (first step, or the weights were changed behind its back) or
+     the target is fp64 (then only the target blocks run)
+  2-7. as above
+  8. step_finalize_update: step_finalize, and the thread that stores a
+     gradient element updates the fp32 master and the optimizer state in
+     place and writes the bf16 image of the new weight into the staged
+     buffers the next step reads
+so a steady-state step is 7 launches (6 with the grouped wgrad) and no
+optimizer kernels. Not capturable in a graph: the AdamW scalars that
+depend on the step count are launch arguments. The composed path (FakeHip CPU mirror, grad_hook
 staging, _NATIVE_GLUE off) runs the same heavy kernels through the three
 older bindings with torch ops as glue (~28 launches).
 Activations a1/a2 and gradients dz never exist in row-major form: the
@@ -255,10 +267,17 @@ def _flat_outs(lin):
     return outs
 
 
+def _world_size() -> int:
+    dist = torch.distributed
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size()
+    return 1
+
+
 def fused_step(
     model: TabularMLP, x: torch.Tensor, target: torch.Tensor,
     grad_hook=None, loss: str = "mse", sample_weight=None,
-    pos_weight=None,
+    pos_weight=None, optimizer=None,
 ) -> Tuple[torch.Tensor, None]:
     """One manual fwd+bwd: computes the loss and POPULATES .grad on
     every parameter of ``model`` (fp32, ready for an optimizer step).
@@ -284,7 +303,16 @@ def fused_step(
     are in their views (right after the backward chain, BEFORE the
     wgrad kernels), then ``grad_hook("w1"|"w2"|"w3")`` after each weight
     grad copy. Lets the caller overlap per-slice gradient collectives
-    with the remaining wgrad kernels (bench RSDL_OVERLAP_ALLREDUCE)."""
+    with the remaining wgrad kernels (bench RSDL_OVERLAP_ALLREDUCE).
+
+    ``optimizer``: a models.fused_optim.FusedOptimizer of ``model``. The
+    step then also applies its update, bit-identical to this call without
+    ``optimizer=`` followed by ``optimizer.step()`` — loss, ``.grad``
+    (still populated), parameters, state and staged buffers — and on the
+    native path inside the same extension call. Every other path (CPU
+    stand-ins, ``grad_hook``, _NATIVE_GLUE off, flat-grad mode in a world
+    larger than one, where the gradients must be reduced first) runs
+    exactly that pair. None (the default) changes nothing."""
     if loss not in _LOSSES:
         raise ValueError(
             f"fused_step: loss must be 'mse' or 'bce', got {loss!r}")
@@ -301,26 +329,43 @@ def fused_step(
     has_weights = bool(getattr(hip, "HEAD_WEIGHTS", 0))
     from ray_shuffling_data_loader_amd.ops.shuffle_ops import wgrad_frag
 
-    if _native_ok(hip, lin, x, target, grad_hook) and (
-            not weighted or (has_weights and (
-                sample_weight is None or sample_weight.device == x.device))):
-        flat_mode = getattr(model, "_rsdl_flat_grads", False)
-        outs = _flat_outs(lin) if flat_mode else None
-        if not flat_mode or outs is not None:
-            res = hip.fused_step_bf16(
-                x, target,
-                [m.weight.detach() for m in lin],
-                [m.bias.detach() for m in lin],
-                pi16=_PI16, outs=outs, **_rows_kw(), **_loss_kw(loss_code),
-                **_weight_kw(sample_weight, pos_weight), **_wgrad_kw(),
-            )
-            if outs is None:
-                # dW1..dW4 then db1..db4, fresh fp32 tensors in the
-                # parameters' shapes.
-                for i, m in enumerate(lin):
-                    m.weight.grad = res[1 + i]
-                    m.bias.grad = res[5 + i]
-            return res[0]
+    native = _native_ok(hip, lin, x, target, grad_hook) and (
+        not weighted or (has_weights and (
+            sample_weight is None or sample_weight.device == x.device)))
+    flat_mode = getattr(model, "_rsdl_flat_grads", False)
+    outs = _flat_outs(lin) if native and flat_mode else None
+    native = native and (not flat_mode or outs is not None)
+    opt_kw = {}
+    if optimizer is not None:
+        if optimizer.model is not model:
+            raise ValueError(
+                "fused_step: optimizer was built for another model")
+        params = optimizer._params()
+        if not (native and optimizer._native(hip, params)
+                and not (flat_mode and _world_size() > 1)):
+            step_loss = fused_step(model, x, target, grad_hook, loss_name,
+                                   sample_weight, pos_weight)
+            optimizer.step()
+            return step_loss
+        opt_kw = {"opt": optimizer._opt_arg(params)}
+    if native:
+        res = hip.fused_step_bf16(
+            x, target,
+            [m.weight.detach() for m in lin],
+            [m.bias.detach() for m in lin],
+            pi16=_PI16, outs=outs, **_rows_kw(), **_loss_kw(loss_code),
+            **_weight_kw(sample_weight, pos_weight), **_wgrad_kw(),
+            **opt_kw,
+        )
+        if optimizer is not None:
+            optimizer._updated(params)
+        if outs is None:
+            # dW1..dW4 then db1..db4, fresh fp32 tensors in the
+            # parameters' shapes.
+            for i, m in enumerate(lin):
+                m.weight.grad = res[1 + i]
+                m.bias.grad = res[5 + i]
+        return res[0]
 
     buf = _weight_buffers(model, lin)
     b1, b2, b3, b4 = (m.bias.detach() for m in lin)
