@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "chain.h"
+#include "embed.h"
 #include "step_glue.h"
 
 namespace rsdl {
@@ -1917,6 +1918,168 @@ void eval_accumulate(const at::Tensor& part, const at::Tensor& acc,
                          current_stream());
 }
 
+// ---- fused multi-table embedding (csrc/embed.hip) ----
+
+namespace {
+
+void check_embed_dout(const at::Tensor& dout, const at::Tensor& widx,
+                      const at::Tensor& grad, int64_t D, const char* who) {
+  TORCH_CHECK(D == 8 || D == 16 || D == 32, who, ": D must be 8, 16 or 32");
+  TORCH_CHECK(widx.is_cuda() && widx.scalar_type() == at::kInt &&
+                  widx.dim() == 2 && widx.is_contiguous() &&
+                  widx.size(0) >= 1 && widx.size(1) >= 1 &&
+                  widx.size(1) <= kEmbedMaxTables,
+              who, ": widx must be contiguous int32 [B>=1, T<=64] on GPU");
+  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == at::kBFloat16 &&
+                  dout.dim() == 2 && dout.is_contiguous() &&
+                  dout.size(0) == widx.size(0) &&
+                  dout.size(1) == widx.size(1) * D &&
+                  dout.get_device() == widx.get_device() &&
+                  reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 == 0,
+              who, ": dout must be contiguous aligned bf16 [B, T*D] on "
+              "widx's GPU");
+  TORCH_CHECK(grad.is_cuda() && grad.scalar_type() == at::kFloat &&
+                  grad.dim() == 2 && grad.is_contiguous() &&
+                  grad.size(1) == D && grad.size(0) < (int64_t(1) << 31) &&
+                  grad.get_device() == widx.get_device() &&
+                  reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0,
+              who, ": grad must be contiguous aligned fp32 [R < 2^31, D] on "
+              "widx's GPU");
+}
+
+}  // namespace
+
+// indices: T int64 tensors [B] or [B,1], any row stride; tables: T fp32
+// [card_t, D]. Returns (bf16 [B, T*D], wrapped indices int32 [B, T] or an
+// empty tensor when want_widx is false).
+std::tuple<at::Tensor, at::Tensor> embed_concat_fwd(
+    const std::vector<at::Tensor>& indices,
+    const std::vector<at::Tensor>& tables, bool want_widx) {
+  const int64_t T = (int64_t)tables.size();
+  TORCH_CHECK(T >= 1 && T <= kEmbedMaxTables,
+              "embed_concat_fwd: 1 to 64 tables, got ", T);
+  TORCH_CHECK((int64_t)indices.size() == T,
+              "embed_concat_fwd: one index tensor per table");
+  const int64_t D = tables[0].dim() == 2 ? tables[0].size(1) : 0;
+  TORCH_CHECK(D == 8 || D == 16 || D == 32,
+              "embed_concat_fwd: D must be 8, 16 or 32");
+  const int64_t B = indices[0].size(0);
+  TORCH_CHECK(B >= 1, "embed_concat_fwd: B must be at least 1");
+  const auto dev = tables[0].get_device();
+  EmbedFwdArgs a{};
+  for (int64_t t = 0; t < T; t++) {
+    const at::Tensor& w = tables[t];
+    const at::Tensor& x = indices[t];
+    TORCH_CHECK(w.is_cuda() && w.get_device() == dev &&
+                    w.scalar_type() == at::kFloat && w.dim() == 2 &&
+                    w.is_contiguous() && w.size(1) == D && w.size(0) >= 1 &&
+                    w.size(0) < (int64_t(1) << 31) &&
+                    reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                "embed_concat_fwd: table ", t,
+                " must be contiguous aligned fp32 [1 <= card < 2^31, ", D,
+                "] on one GPU");
+    TORCH_CHECK(x.is_cuda() && x.get_device() == dev &&
+                    x.scalar_type() == at::kLong &&
+                    (x.dim() == 1 || (x.dim() == 2 && x.size(1) == 1)) &&
+                    x.size(0) == B && x.stride(0) >= 0,
+                "embed_concat_fwd: index ", t,
+                " must be int64 [B] or [B,1] on the tables' GPU");
+    a.idx[t] = x.data_ptr<int64_t>();
+    a.stride[t] = x.stride(0);
+    a.W[t] = w.data_ptr<float>();
+    a.card[t] = (int32_t)w.size(0);
+  }
+  auto out = at::empty({B, T * D}, tables[0].options().dtype(at::kBFloat16));
+  at::Tensor widx;
+  if (want_widx) {
+    widx = at::empty({B, T}, tables[0].options().dtype(at::kInt));
+  } else {
+    widx = at::empty({0}, tables[0].options().dtype(at::kInt));
+  }
+  launch_embed_concat_fwd(a, out.data_ptr(),
+                          want_widx ? widx.data_ptr<int32_t>() : nullptr, B,
+                          (int32_t)T, (int32_t)D, current_stream());
+  return {out, widx};
+}
+
+// Dense-regime backward of the tables ``slots`` (table numbers), whose
+// gradients are the rows [row_offs[i], row_offs[i] + cards[i]) of the flat
+// ``grad`` [R, D]: every such row is overwritten.
+void embed_bwd_onehot(const at::Tensor& dout, const at::Tensor& widx,
+                      const at::Tensor& grad,
+                      const std::vector<int64_t>& slots,
+                      const std::vector<int64_t>& cards,
+                      const std::vector<int64_t>& row_offs) {
+  const int64_t D = grad.dim() == 2 ? grad.size(1) : 0;
+  check_embed_dout(dout, widx, grad, D, "embed_bwd_onehot");
+  const int64_t n = (int64_t)slots.size();
+  TORCH_CHECK(n >= 1 && n <= kEmbedMaxTables &&
+                  (int64_t)cards.size() == n && (int64_t)row_offs.size() == n,
+              "embed_bwd_onehot: 1 to 64 tables with one cardinality and "
+              "row offset each");
+  const int64_t B = widx.size(0), T = widx.size(1);
+  // At least 64 slabs per table where the batch allows, 256 rows or more
+  // each, at most what the LDS holds.
+  int64_t S = (((B + 63) / 64) + 15) / 16 * 16;
+  S = std::min<int64_t>(embed_max_slab((int32_t)D), std::max<int64_t>(256, S));
+  const int64_t nslab = (B + S - 1) / S;
+  TORCH_CHECK(nslab <= 65535, "embed_bwd_onehot: batch too large");
+  EmbedBwdArgs a{};
+  int64_t part_floats = 0, max_card = 0;
+  for (int64_t i = 0; i < n; i++) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < T && cards[i] >= 1 &&
+                    cards[i] <= (1 << 20) && row_offs[i] >= 0 &&
+                    row_offs[i] + cards[i] <= grad.size(0),
+                "embed_bwd_onehot: table ", i, " out of range");
+    a.t[i] = (int32_t)slots[i];
+    a.card[i] = (int32_t)cards[i];
+    a.row_off[i] = row_offs[i];
+    a.part_off[i] = part_floats;
+    part_floats += nslab * ((cards[i] + 31) / 32 * 32) * D;
+    max_card = std::max(max_card, cards[i]);
+  }
+  auto part = at::empty({part_floats}, grad.options());
+  launch_embed_bwd_onehot(a, (int32_t)n, widx.data_ptr<int32_t>(),
+                          dout.data_ptr(), part.data_ptr<float>(),
+                          grad.data_ptr<float>(), B, (int32_t)T, (int32_t)D,
+                          (int32_t)S, (int32_t)nslab, (int32_t)max_card,
+                          current_stream());
+}
+
+// Sorted-regime backward. keys int32 [n*B] ascending: the flat grad row of
+// each (entry, batch row); pos int64 [n*B]: entry * B + batch row, as a
+// stable sort returns it. Precondition, NOT checked: keys lie in [0, R) and
+// pos is a permutation of [0, n*B); anything else reads or writes out of
+// bounds. Rows no key names are left alone.
+void embed_bwd_runs(const at::Tensor& dout, const at::Tensor& widx,
+                    const at::Tensor& grad, const at::Tensor& keys,
+                    const at::Tensor& pos,
+                    const std::vector<int64_t>& slots) {
+  const int64_t D = grad.dim() == 2 ? grad.size(1) : 0;
+  check_embed_dout(dout, widx, grad, D, "embed_bwd_runs");
+  const int64_t n = (int64_t)slots.size();
+  const int64_t B = widx.size(0), T = widx.size(1);
+  TORCH_CHECK(n >= 1 && n <= kEmbedMaxTables,
+              "embed_bwd_runs: 1 to 64 tables");
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == at::kInt &&
+                  keys.is_contiguous() && keys.numel() == n * B &&
+                  pos.is_cuda() && pos.scalar_type() == at::kLong &&
+                  pos.is_contiguous() && pos.numel() == n * B &&
+                  keys.get_device() == widx.get_device() &&
+                  pos.get_device() == widx.get_device(),
+              "embed_bwd_runs: keys int32 and pos int64, contiguous [n*B] on "
+              "widx's GPU");
+  EmbedBwdArgs a{};
+  for (int64_t i = 0; i < n; i++) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < T,
+                "embed_bwd_runs: table ", i, " out of range");
+    a.t[i] = (int32_t)slots[i];
+  }
+  launch_embed_bwd_runs(a, keys.data_ptr<int32_t>(), pos.data_ptr<int64_t>(),
+                        dout.data_ptr(), grad.data_ptr<float>(), n * B, B,
+                        (int32_t)T, (int32_t)D, current_stream());
+}
+
 }  // namespace rsdl
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2032,6 +2195,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight") = c10::nullopt);
   m.def("eval_accumulate", &rsdl::eval_accumulate, py::arg("part"),
         py::arg("acc"), py::arg("M"));
+  m.def("embed_concat_fwd", &rsdl::embed_concat_fwd,
+        "(bf16 [B, T*D], int32 [B, T] wrapped indices): out[b, t*D:(t+1)*D] "
+        "= bf16(tables[t][max(indices[t][b], 0) % card_t]), one launch.",
+        py::arg("indices"), py::arg("tables"), py::arg("want_widx") = true);
+  m.def("embed_bwd_onehot", &rsdl::embed_bwd_onehot, py::arg("dout"),
+        py::arg("widx"), py::arg("grad"), py::arg("slots"), py::arg("cards"),
+        py::arg("row_offs"));
+  m.def("embed_bwd_runs", &rsdl::embed_bwd_runs, py::arg("dout"),
+        py::arg("widx"), py::arg("grad"), py::arg("keys"), py::arg("pos"),
+        py::arg("slots"));
   m.attr("LOSS_MSE") = (int)rsdl::kLossMse;
   m.attr("LOSS_BCE") = (int)rsdl::kLossBce;
   // the heads take sample weights / pos_weight (weight=, pos_weight=)

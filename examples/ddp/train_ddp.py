@@ -45,7 +45,7 @@ from ray_shuffling_data_loader_amd.parallel import fabric
 from ray_shuffling_data_loader_amd.torch_dataset import TorchShufflingDataset
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--num-rows", type=int, default=2 * 10**7)
     p.add_argument("--num-files", type=int, default=25)
@@ -94,8 +94,17 @@ def parse_args():
                    "optimizer= and the update runs inside the step; more "
                    "run fused_step -> one flat gradient all-reduce -> "
                    "opt.step(grad_scale=1/world)")
+    p.add_argument("--fused-embedding", action="store_true",
+                   help="EmbeddingMLP path (--spec tabular): run the 19 "
+                   "lookups and the concat as one HIP launch with a "
+                   "deterministic backward "
+                   "(models.fused_embedding.fused_embedding)")
     p.add_argument("--device", type=str, default=None)
-    return p.parse_args()
+    args = p.parse_args(argv)
+    if args.fused_embedding and args.spec != "tabular":
+        raise SystemExit("--fused-embedding is for the EmbeddingMLP path "
+                         "(--spec tabular)")
+    return args
 
 
 def fused_train_setup(args, model, world, device):
@@ -215,7 +224,9 @@ def train_main(args, world, rank):
             label_column="labels",
             device=device,
         )
-        model = EmbeddingMLP(cardinalities).to(device)
+        model = EmbeddingMLP(
+            cardinalities, fused_embedding=args.fused_embedding
+        ).to(device)
     else:
         feature_columns = [f"f{i}" for i in range(args.num_cols)]
         ds = TorchShufflingDataset(

@@ -237,10 +237,21 @@ class TabularMLP(nn.Module):
 class EmbeddingMLP(nn.Module):
     """Model shaped for the reference DATA_SPEC batches: 19 int64
     categorical columns -> embeddings, concatenated -> MLP
-    (the realistic counterpart of the reference example's unused Net)."""
+    (the realistic counterpart of the reference example's unused Net).
 
-    def __init__(self, cardinalities, embed_dim: int = 16, hidden: int = 256):
+    ``fused_embedding=True`` runs the lookups and the concat as one HIP
+    launch with a deterministic backward (models/fused_embedding.py);
+    parameter names and shapes are the same either way."""
+
+    def __init__(
+        self,
+        cardinalities,
+        embed_dim: int = 16,
+        hidden: int = 256,
+        fused_embedding: bool = False,
+    ):
         super().__init__()
+        self.fused_embedding = bool(fused_embedding)
         self.embeddings = nn.ModuleList(
             [
                 nn.Embedding(int(c), embed_dim)
@@ -255,6 +266,21 @@ class EmbeddingMLP(nn.Module):
         )
 
     def forward(self, cat_feats) -> torch.Tensor:
+        if self.fused_embedding:
+            from ray_shuffling_data_loader_amd.models.fused_embedding import (
+                fused_embedding,
+            )
+
+            x = fused_embedding(
+                cat_feats, [emb.weight for emb in self.embeddings]
+            )
+            # the dtype the first Linear runs in: bf16 under the
+            # project's autocast, where this is no cast at all
+            if x.is_cuda and torch.is_autocast_enabled():
+                dt = torch.get_autocast_dtype("cuda")
+            else:
+                dt = self.mlp[0].weight.dtype
+            return self.mlp(x.to(dt))
         embs = [
             emb(x.clamp_min(0).squeeze(-1) % emb.num_embeddings)
             for emb, x in zip(self.embeddings, cat_feats)

@@ -47,6 +47,7 @@ try:
         "csrc/wgrad_wide.hip",
         "csrc/wgrad_frag.hip",
         "csrc/step_glue.hip",
+        "csrc/embed.hip",
     ]
     if all(os.path.exists(s) for s in hip_sources):
         ext_modules.append(
