@@ -307,6 +307,21 @@ void launch_embed_bwd_onehot(const EmbedBwdArgs& a, int32_t n,
 #undef EM_ONEHOT
 }
 
+void launch_embed_onehot_partials(const EmbedBwdArgs& a, int32_t n,
+                                  const int32_t* widx, const void* dout,
+                                  float* part, int64_t B, int32_t T,
+                                  int32_t D, int32_t S, int32_t nslab,
+                                  hipStream_t stream) {
+  const size_t lds = (size_t)S * 4 + (size_t)D * (S + 8) * 2;
+#define EM_PARTIALS(W)                                                    \
+  hipLaunchKernelGGL(embed_bwd_onehot_kernel<W>, dim3(n, nslab),          \
+                     dim3(EM_THREADS), lds, stream, a, widx,              \
+                     reinterpret_cast<const uint16_t*>(dout), part, B, T, \
+                     S)
+  EMBED_BY_WIDTH(D, EM_PARTIALS)
+#undef EM_PARTIALS
+}
+
 void launch_embed_bwd_runs(const EmbedBwdArgs& a, const int32_t* keys,
                            const int64_t* pos, const void* dout, float* grad,
                            int64_t N, int64_t B, int32_t T, int32_t D,

@@ -1947,6 +1947,59 @@ void check_embed_dout(const at::Tensor& dout, const at::Tensor& widx,
               "widx's GPU");
 }
 
+// Rows of a batch slab of the one-hot regime: at least 64 slabs per table
+// where the batch allows, 256 rows or more each, at most what the LDS holds.
+int64_t embed_slab_rows(int64_t B, int64_t D) {
+  const int64_t S = (((B + 63) / 64) + 15) / 16 * 16;
+  return std::min<int64_t>(embed_max_slab((int32_t)D),
+                           std::max<int64_t>(256, S));
+}
+
+// Tables and optimizer state of the update bindings -> a.W / a.state /
+// a.card; n entries on widx's GPU.
+void fill_embed_opt(EmbedOptArgs& a, const at::Tensor& widx, int64_t D,
+                    const std::vector<at::Tensor>& tables,
+                    const std::vector<at::Tensor>& states, int64_t kind,
+                    double lr, double eps, const char* who) {
+  const int64_t n = (int64_t)tables.size();
+  TORCH_CHECK(kind == kEmbedSgd || kind == kEmbedAdagrad ||
+                  kind == kEmbedRowwiseAdagrad,
+              who, ": kind must be 0 (sgd), 1 (adagrad) or 2 (rowwise "
+              "adagrad)");
+  TORCH_CHECK(std::isfinite(lr) && std::isfinite(eps) && lr >= 0.0 &&
+                  (kind == kEmbedSgd ? eps >= 0.0 : eps > 0.0),
+              who, ": lr must be finite and >= 0, eps finite and > 0");
+  TORCH_CHECK((int64_t)states.size() == (kind == kEmbedSgd ? 0 : n), who,
+              ": one state tensor per table (none for sgd)");
+  for (int64_t i = 0; i < n; i++) {
+    const at::Tensor& w = tables[i];
+    TORCH_CHECK(w.is_cuda() && w.get_device() == widx.get_device() &&
+                    w.scalar_type() == at::kFloat && w.dim() == 2 &&
+                    w.is_contiguous() && w.size(1) == D && w.size(0) >= 1 &&
+                    w.size(0) < (int64_t(1) << 31) &&
+                    reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                who, ": table ", i,
+                " must be contiguous aligned fp32 [1 <= card < 2^31, ", D,
+                "] on widx's GPU");
+    a.W[i] = w.data_ptr<float>();
+    a.card[i] = (int32_t)w.size(0);
+    if (kind == kEmbedSgd) continue;
+    const at::Tensor& h = states[i];
+    const bool row = kind == kEmbedRowwiseAdagrad;
+    TORCH_CHECK(h.is_cuda() && h.get_device() == widx.get_device() &&
+                    h.scalar_type() == at::kFloat && h.is_contiguous() &&
+                    h.dim() == (row ? 1 : 2) && h.size(0) == w.size(0) &&
+                    (row || h.size(1) == D) &&
+                    reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
+                who, ": state ", i, " must be contiguous aligned fp32 ",
+                row ? "[card]" : "[card, D]", " on widx's GPU");
+    a.state[i] = h.data_ptr<float>();
+  }
+  a.kind = (int32_t)kind;
+  a.lr = (float)lr;
+  a.eps = (float)eps;
+}
+
 }  // namespace
 
 // indices: T int64 tensors [B] or [B,1], any row stride; tables: T fp32
@@ -2018,10 +2071,7 @@ void embed_bwd_onehot(const at::Tensor& dout, const at::Tensor& widx,
               "embed_bwd_onehot: 1 to 64 tables with one cardinality and "
               "row offset each");
   const int64_t B = widx.size(0), T = widx.size(1);
-  // At least 64 slabs per table where the batch allows, 256 rows or more
-  // each, at most what the LDS holds.
-  int64_t S = (((B + 63) / 64) + 15) / 16 * 16;
-  S = std::min<int64_t>(embed_max_slab((int32_t)D), std::max<int64_t>(256, S));
+  const int64_t S = embed_slab_rows(B, D);
   const int64_t nslab = (B + S - 1) / S;
   TORCH_CHECK(nslab <= 65535, "embed_bwd_onehot: batch too large");
   EmbedBwdArgs a{};
@@ -2078,6 +2128,111 @@ void embed_bwd_runs(const at::Tensor& dout, const at::Tensor& widx,
   launch_embed_bwd_runs(a, keys.data_ptr<int32_t>(), pos.data_ptr<int64_t>(),
                         dout.data_ptr(), grad.data_ptr<float>(), n * B, B,
                         (int32_t)T, (int32_t)D, current_stream());
+}
+
+// In-place optimizer update of the small tables ``slots`` (table numbers)
+// from this batch: one-hot slab partials as embed_bwd_onehot, then the fold
+// applies ``kind`` to every row of tables[i] and states[i]. No gradient
+// buffer exists.
+void embed_onehot_update(const at::Tensor& dout, const at::Tensor& widx,
+                         const std::vector<int64_t>& slots,
+                         const std::vector<at::Tensor>& tables,
+                         const std::vector<at::Tensor>& states, int64_t kind,
+                         double lr, double eps) {
+  const int64_t n = (int64_t)slots.size();
+  TORCH_CHECK(n >= 1 && n <= kEmbedMaxTables && (int64_t)tables.size() == n,
+              "embed_onehot_update: 1 to 64 tables, one tensor each");
+  const int64_t D = tables[0].dim() == 2 ? tables[0].size(1) : 0;
+  EmbedOptArgs o{};
+  fill_embed_opt(o, widx, D, tables, states, kind, lr, eps,
+                 "embed_onehot_update");
+  check_embed_dout(dout, widx, tables[0], D, "embed_onehot_update");
+  const int64_t B = widx.size(0), T = widx.size(1);
+  const int64_t S = embed_slab_rows(B, D);
+  const int64_t nslab = (B + S - 1) / S;
+  TORCH_CHECK(nslab <= 65535, "embed_onehot_update: batch too large");
+  EmbedBwdArgs a{};
+  int64_t part_floats = 0, max_card = 0;
+  for (int64_t i = 0; i < n; i++) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < T && o.card[i] <= (1 << 20),
+                "embed_onehot_update: table ", i, " out of range");
+    for (int64_t j = 0; j < i; j++) {
+      TORCH_CHECK(o.W[j] != o.W[i], "embed_onehot_update: table ", i,
+                  " is given twice");
+    }
+    a.t[i] = o.t[i] = (int32_t)slots[i];
+    a.card[i] = o.card[i];
+    a.part_off[i] = o.part_off[i] = part_floats;
+    part_floats += nslab * ((o.card[i] + 31) / 32 * 32) * D;
+    max_card = std::max<int64_t>(max_card, o.card[i]);
+  }
+  auto part = at::empty({part_floats}, tables[0].options());
+  launch_embed_onehot_partials(a, (int32_t)n, widx.data_ptr<int32_t>(),
+                               dout.data_ptr(), part.data_ptr<float>(), B,
+                               (int32_t)T, (int32_t)D, (int32_t)S,
+                               (int32_t)nslab, current_stream());
+  launch_embed_fold_update(o, (int32_t)n, part.data_ptr<float>(), (int32_t)D,
+                           (int32_t)nslab, (int32_t)max_card,
+                           current_stream());
+  bump_versions(tables, states, {});
+}
+
+// In-place optimizer update of the large tables ``slots`` from this batch.
+// keys, pos as for embed_bwd_runs, with row_offs[i] the first key of entry
+// i: key - row_offs[i] is the row of tables[i]. Precondition, NOT checked:
+// pos is a permutation of [0, n*B) and every key of entry i lies in
+// [row_offs[i], row_offs[i] + card_i); anything else reads or writes out of
+// bounds. Only the rows the keys name are read or written.
+void embed_runs_update(const at::Tensor& dout, const at::Tensor& widx,
+                       const at::Tensor& keys, const at::Tensor& pos,
+                       const std::vector<int64_t>& slots,
+                       const std::vector<int64_t>& row_offs,
+                       const std::vector<at::Tensor>& tables,
+                       const std::vector<at::Tensor>& states, int64_t kind,
+                       double lr, double eps) {
+  const int64_t n = (int64_t)slots.size();
+  TORCH_CHECK(n >= 1 && n <= kEmbedMaxTables && (int64_t)tables.size() == n &&
+                  (int64_t)row_offs.size() == n,
+              "embed_runs_update: 1 to 64 tables with one tensor and row "
+              "offset each");
+  const int64_t D = tables[0].dim() == 2 ? tables[0].size(1) : 0;
+  EmbedOptArgs o{};
+  fill_embed_opt(o, widx, D, tables, states, kind, lr, eps,
+                 "embed_runs_update");
+  check_embed_dout(dout, widx, tables[0], D, "embed_runs_update");
+  const int64_t B = widx.size(0), T = widx.size(1);
+  const int64_t N = n * B;
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == at::kInt &&
+                  keys.is_contiguous() && keys.numel() == N &&
+                  pos.is_cuda() && pos.scalar_type() == at::kLong &&
+                  pos.is_contiguous() && pos.numel() == N &&
+                  keys.get_device() == widx.get_device() &&
+                  pos.get_device() == widx.get_device() &&
+                  reinterpret_cast<uintptr_t>(keys.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(pos.data_ptr()) % 16 == 0,
+              "embed_runs_update: keys int32 and pos int64, contiguous "
+              "aligned [n*B] on widx's GPU");
+  for (int64_t i = 0; i < n; i++) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < T && row_offs[i] >= 0 &&
+                    row_offs[i] + o.card[i] <= (int64_t(1) << 31) &&
+                    (i == 0 ||
+                     row_offs[i] >= row_offs[i - 1] + o.card[i - 1]),
+                "embed_runs_update: table ", i, " out of range, or row "
+                "offsets that overlap or do not ascend");
+    for (int64_t j = 0; j < i; j++) {
+      TORCH_CHECK(o.W[j] != o.W[i], "embed_runs_update: table ", i,
+                  " is given twice");
+    }
+    o.t[i] = (int32_t)slots[i];
+    o.row_off[i] = row_offs[i];
+  }
+  const int64_t chunks = (N + 15) / 16;
+  auto carry = at::empty({chunks * 2 * D}, tables[0].options());
+  launch_embed_runs_update(o, keys.data_ptr<int32_t>(),
+                           pos.data_ptr<int64_t>(), dout.data_ptr(),
+                           carry.data_ptr<float>(), N, B, (int32_t)T,
+                           (int32_t)D, current_stream());
+  bump_versions(tables, states, {});
 }
 
 }  // namespace rsdl
@@ -2205,6 +2360,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_bwd_runs", &rsdl::embed_bwd_runs, py::arg("dout"),
         py::arg("widx"), py::arg("grad"), py::arg("keys"), py::arg("pos"),
         py::arg("slots"));
+  m.def("embed_onehot_update", &rsdl::embed_onehot_update, py::arg("dout"),
+        py::arg("widx"), py::arg("slots"), py::arg("tables"),
+        py::arg("states"), py::arg("kind"), py::arg("lr"), py::arg("eps"));
+  m.def("embed_runs_update", &rsdl::embed_runs_update, py::arg("dout"),
+        py::arg("widx"), py::arg("keys"), py::arg("pos"), py::arg("slots"),
+        py::arg("row_offs"), py::arg("tables"), py::arg("states"),
+        py::arg("kind"), py::arg("lr"), py::arg("eps"));
+  // embed_onehot_update / embed_runs_update
+  m.attr("EMBED_OPTIM") = 1;
+  m.attr("EMBED_SGD") = (int)rsdl::kEmbedSgd;
+  m.attr("EMBED_ADAGRAD") = (int)rsdl::kEmbedAdagrad;
+  m.attr("EMBED_ROWWISE_ADAGRAD") = (int)rsdl::kEmbedRowwiseAdagrad;
   m.attr("LOSS_MSE") = (int)rsdl::kLossMse;
   m.attr("LOSS_BCE") = (int)rsdl::kLossBce;
   // the heads take sample weights / pos_weight (weight=, pos_weight=)

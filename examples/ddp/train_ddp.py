@@ -99,11 +99,26 @@ def parse_args(argv=None):
                    "lookups and the concat as one HIP launch with a "
                    "deterministic backward "
                    "(models.fused_embedding.fused_embedding)")
+    p.add_argument("--embedding-optimizer",
+                   choices=["torch", "sgd", "adagrad", "rowwise-adagrad"],
+                   default="torch",
+                   help="torch: the tables get dense gradients and the "
+                   "torch optimizer steps them (the default). sgd / adagrad "
+                   "/ rowwise-adagrad (--spec tabular --fused-embedding, "
+                   "one process): a models.fused_embedding."
+                   "FusedEmbeddingOptimizer updates only the rows a batch "
+                   "touched, with no gradient buffer; the MLP keeps the "
+                   "torch optimizer")
     p.add_argument("--device", type=str, default=None)
     args = p.parse_args(argv)
     if args.fused_embedding and args.spec != "tabular":
         raise SystemExit("--fused-embedding is for the EmbeddingMLP path "
                          "(--spec tabular)")
+    if args.embedding_optimizer != "torch" and not (
+            args.spec == "tabular" and args.fused_embedding):
+        raise SystemExit("--embedding-optimizer sgd / adagrad / "
+                         "rowwise-adagrad needs --spec tabular "
+                         "--fused-embedding")
     return args
 
 
@@ -224,9 +239,27 @@ def train_main(args, world, rank):
             label_column="labels",
             device=device,
         )
+        embed_opt = None
+        if args.embedding_optimizer != "torch":
+            if world > 1:
+                raise SystemExit("--embedding-optimizer sgd / adagrad / "
+                                 "rowwise-adagrad runs in one process: "
+                                 "sparse gradients are not exchanged")
+            import functools
+
+            from ray_shuffling_data_loader_amd.models.fused_embedding import (
+                FusedEmbeddingOptimizer,
+            )
+
+            embed_opt = functools.partial(
+                FusedEmbeddingOptimizer,
+                kind=args.embedding_optimizer.replace("-", "_"), lr=args.lr,
+            )
         model = EmbeddingMLP(
-            cardinalities, fused_embedding=args.fused_embedding
+            cardinalities, fused_embedding=args.fused_embedding,
+            embedding_optimizer=embed_opt,
         ).to(device)
+        embed_opt = model.embedding_optimizer
     else:
         feature_columns = [f"f{i}" for i in range(args.num_cols)]
         ds = TorchShufflingDataset(
@@ -244,6 +277,7 @@ def train_main(args, world, rank):
             device=device,
         )
         model = TabularMLP(args.num_cols).to(device)
+        embed_opt = None
     fused = args.optimizer != "torch"
     if fused and (tabular or args.num_cols != 100
                   or args.mock_train_step_time is not None):
@@ -263,7 +297,11 @@ def train_main(args, world, rank):
     if fused:
         opt, flat = fused_train_setup(args, model, world, device)
     else:
-        opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9)
+        # with an embedding optimizer the tables are not torch's to step
+        opt = torch.optim.SGD(
+            model.mlp.parameters() if embed_opt is not None
+            else model.parameters(),
+            lr=args.lr, momentum=0.9)
     if args.loss == "bce" and tabular:
         raise SystemExit("--loss bce is for the TabularMLP path "
                          "(--spec float)")
@@ -325,6 +363,8 @@ def train_main(args, world, rank):
                     loss = loss_fn(model(x), target, weight)
                     loss.backward()
                     opt.step()
+                    if embed_opt is not None:
+                        embed_opt.step()
                 n_batches += 1
                 t_wait = time.perf_counter()
             if fused and world > 1:

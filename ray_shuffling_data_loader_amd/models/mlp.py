@@ -241,7 +241,15 @@ class EmbeddingMLP(nn.Module):
 
     ``fused_embedding=True`` runs the lookups and the concat as one HIP
     launch with a deterministic backward (models/fused_embedding.py);
-    parameter names and shapes are the same either way."""
+    parameter names and shapes are the same either way.
+
+    ``embedding_optimizer`` (with ``fused_embedding=True``) is passed
+    through as ``fused_embedding(optimizer=)``: the tables then get no
+    ``.grad`` and are stepped by it, not by the optimizer of ``mlp``. It is
+    a ``FusedEmbeddingOptimizer`` bound to these tables or, since the tables
+    are made here, a callable that builds one from the list of them
+    (``functools.partial(FusedEmbeddingOptimizer, kind="adagrad")``); the
+    attribute ``embedding_optimizer`` holds the optimizer either way."""
 
     def __init__(
         self,
@@ -249,9 +257,14 @@ class EmbeddingMLP(nn.Module):
         embed_dim: int = 16,
         hidden: int = 256,
         fused_embedding: bool = False,
+        embedding_optimizer=None,
     ):
         super().__init__()
         self.fused_embedding = bool(fused_embedding)
+        if embedding_optimizer is not None and not self.fused_embedding:
+            raise ValueError(
+                "EmbeddingMLP: embedding_optimizer needs fused_embedding=True"
+            )
         self.embeddings = nn.ModuleList(
             [
                 nn.Embedding(int(c), embed_dim)
@@ -264,6 +277,11 @@ class EmbeddingMLP(nn.Module):
             nn.ReLU(),
             nn.Linear(hidden, 1),
         )
+        if callable(embedding_optimizer):
+            embedding_optimizer = embedding_optimizer(
+                [emb.weight for emb in self.embeddings]
+            )
+        self.embedding_optimizer = embedding_optimizer
 
     def forward(self, cat_feats) -> torch.Tensor:
         if self.fused_embedding:
@@ -272,7 +290,8 @@ class EmbeddingMLP(nn.Module):
             )
 
             x = fused_embedding(
-                cat_feats, [emb.weight for emb in self.embeddings]
+                cat_feats, [emb.weight for emb in self.embeddings],
+                optimizer=self.embedding_optimizer,
             )
             # the dtype the first Linear runs in: bf16 under the
             # project's autocast, where this is no cast at all

@@ -48,6 +48,7 @@ try:
         "csrc/wgrad_frag.hip",
         "csrc/step_glue.hip",
         "csrc/embed.hip",
+        "csrc/embed_optim.hip",
     ]
     if all(os.path.exists(s) for s in hip_sources):
         ext_modules.append(
