@@ -39,7 +39,7 @@ def make_tables(cards, D, device, seed=1):
 
 
 def exact_dout(B, width, device, seed=2):
-    """Integers in [-8, 8] times 2^-3: exact in bf16, and with B <= 1000
+    """Integers in [-8, 8] times 2^-3: exact in bf16, and with B < 2^21
     every partial sum is a multiple of 2^-3 below 2^21, exact in fp32 in
     any order."""
     g = torch.Generator().manual_seed(seed)
