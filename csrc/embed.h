@@ -50,22 +50,32 @@ struct EmbedOptArgs {
   float eps;
 };
 
+// embed_bwd_onehot stages at most 32 columns of dOut: wider tables are cut
+// into D / 32 column slices, one workgroup each (the grid's z axis).
+inline int32_t embed_slices(int32_t D) { return D > 32 ? D / 32 : 1; }
+
 // Rows of a batch slab of embed_bwd_onehot at width D: the largest whose
-// staged indices and transposed dOut slice fit 64 KB of LDS.
-inline int32_t embed_max_slab(int32_t D) { return 16384 / D; }
+// staged indices and transposed dOut slice (of min(D, 32) columns) fit
+// 64 KB of LDS.
+inline int32_t embed_max_slab(int32_t D) {
+  return 16384 / (D / embed_slices(D));
+}
 
 // out bf16 [B, T*D]; widx int32 [B, T] wrapped indices, or nullptr.
 void launch_embed_concat_fwd(const EmbedFwdArgs& a, void* out, int32_t* widx,
                              int64_t B, int32_t T, int32_t D,
                              hipStream_t stream);
 // n entries, nslab slabs of S rows (S a multiple of 16, at most
-// embed_max_slab(D)); part holds [nslab, card_pad, D] per entry at part_off,
-// card_pad = card rounded up to 32. Then the fixed-order fold into grad.
+// embed_max_slab(D)), nslice = embed_slices(D) column slices; part holds
+// [nslab, card_pad, D] per entry at part_off, card_pad = card rounded up to
+// 32, and slice z writes its columns [z * D / nslice, (z + 1) * D / nslice)
+// of it. Then the fixed-order fold into grad.
 void launch_embed_bwd_onehot(const EmbedBwdArgs& a, int32_t n,
                              const int32_t* widx, const void* dout,
                              float* part, float* grad, int64_t B, int32_t T,
                              int32_t D, int32_t S, int32_t nslab,
-                             int32_t max_card, hipStream_t stream);
+                             int32_t nslice, int32_t max_card,
+                             hipStream_t stream);
 // keys int32 [N] ascending (flat grad row of each position), pos int64 [N]
 // (entry * B + batch row, ascending inside equal keys); a.t holds the n
 // entries' table numbers.
@@ -79,7 +89,7 @@ void launch_embed_onehot_partials(const EmbedBwdArgs& a, int32_t n,
                                   const int32_t* widx, const void* dout,
                                   float* part, int64_t B, int32_t T,
                                   int32_t D, int32_t S, int32_t nslab,
-                                  hipStream_t stream);
+                                  int32_t nslice, hipStream_t stream);
 // keys, pos as for launch_embed_bwd_runs, both 16-byte aligned; carry holds
 // ceil(N / 16) * 2 * D floats and need not be cleared. Updates the rows the
 // keys name (key - row_off of the entry) and their state, nothing else.

@@ -36,6 +36,14 @@
 //   LDS: rows of the transposed slice are (S+8)*2 bytes apart = S/2 + 4
 //   dwords, so at S = 1024 the 16 lanes of a B-fragment read start 4 banks
 //   apart and cover the 64 banks once.
+//   D = 64 and 128: the product is cut into 32-column slices on a third
+//   grid axis, grid (table, batch slab, D/32). Workgroup z stages the slab's
+//   indices and only its slice, bf16 [32][S + 8], read in 64-byte row
+//   segments at column t*D + z*32, runs the same wave loop and writes the
+//   columns z*32 .. z*32 + 31 of the slab's [card_pad, D] partial. LDS
+//   footprint, bank pattern and the slab cap of 512 rows are those of
+//   D = 32, and the partials grow with D, not with D^2 as they would with a
+//   slab of 16384 / D rows. Every slice builds the one-hot fragments again.
 //
 // embed_bwd_runs (large tables): the caller sorts the keys (flat gradient
 // row of every (table, batch row)) with a stable sort; D/4 lanes take each
@@ -118,14 +126,20 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
                             const uint16_t* __restrict__ dout,
                             float* __restrict__ part, int64_t B, int32_t T,
                             int32_t S) {
-  constexpr int PPT = D / 8;
+  // Columns this workgroup stages and multiplies: all D up to 32, else the
+  // 32-column slice blockIdx.z. W = D and z = 0 leave the narrow widths
+  // what they were.
+  constexpr int W = D < 32 ? D : 32;
+  constexpr int PPT = W / 8;
+  static_assert(D % W == 0, "whole column slices");
   extern __shared__ __attribute__((aligned(16))) uint8_t em_smem[];
   int32_t* sidx = reinterpret_cast<int32_t*>(em_smem);            // [S]
-  uint16_t* sg = reinterpret_cast<uint16_t*>(em_smem + S * 4);    // [D][LS]
+  uint16_t* sg = reinterpret_cast<uint16_t*>(em_smem + S * 4);    // [W][LS]
   const int32_t LS = S + 8;
 
   const int32_t e = blockIdx.x;
   const int32_t slab = blockIdx.y;
+  const int32_t c0 = D > 32 ? (int32_t)blockIdx.z * W : 0;  // first column
   const int32_t tid = threadIdx.x;
   const int32_t t = a.t[e];
   const int32_t card = a.card[e];
@@ -143,7 +157,7 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (r < nb) {
       v = *reinterpret_cast<const uint4*>(
-          &dout[(b0 + r) * TD + t * D + p * 8]);
+          &dout[(b0 + r) * TD + t * D + c0 + p * 8]);
     }
     uint16_t* col = &sg[(p * 8) * LS + r];
     col[0 * LS] = (uint16_t)v.x;
@@ -179,7 +193,7 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
       const int4 i0 = *reinterpret_cast<const int4*>(&sidx[k0 + kh]);
       const int4 i1 = *reinterpret_cast<const int4*>(&sidx[k0 + kh + 4]);
       em_bf16x8 bfr = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (n < D) {
+      if (n < W) {
         bfr = *reinterpret_cast<const em_bf16x8*>(&sg[n * LS + k0 + kh]);
       }
       const int32_t d[8] = {i0.x - rbase, i0.y - rbase, i0.z - rbase,
@@ -200,12 +214,12 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
     }
     #pragma unroll
     for (int tt = 0; tt < 4; tt++) {
-      if (tt < live && n < D) {
+      if (tt < live && n < W) {
         #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
           const int32_t row = g * 128 + tt * 32 + (reg & 3) + 8 * (reg >> 2) +
                               4 * (lane >> 5);
-          my_part[(int64_t)row * D + n] = acc[tt][reg];
+          my_part[(int64_t)row * D + c0 + n] = acc[tt][reg];
         }
       }
     }
@@ -272,6 +286,8 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
   switch (D) {                  \
     case 8: { CALL(8); break; } \
     case 16: { CALL(16); break; } \
+    case 64: { CALL(64); break; } \
+    case 128: { CALL(128); break; } \
     default: { CALL(32); break; } \
   }
 
@@ -292,12 +308,13 @@ void launch_embed_bwd_onehot(const EmbedBwdArgs& a, int32_t n,
                              const int32_t* widx, const void* dout,
                              float* part, float* grad, int64_t B, int32_t T,
                              int32_t D, int32_t S, int32_t nslab,
-                             int32_t max_card, hipStream_t stream) {
-  const size_t lds = (size_t)S * 4 + (size_t)D * (S + 8) * 2;
+                             int32_t nslice, int32_t max_card,
+                             hipStream_t stream) {
+  const size_t lds = (size_t)S * 4 + (size_t)(D / nslice) * (S + 8) * 2;
   const uint32_t fold_x =
       (uint32_t)((max_card * (D / 4) + EM_THREADS - 1) / EM_THREADS);
 #define EM_ONEHOT(W)                                                      \
-  hipLaunchKernelGGL(embed_bwd_onehot_kernel<W>, dim3(n, nslab),          \
+  hipLaunchKernelGGL(embed_bwd_onehot_kernel<W>, dim3(n, nslab, nslice),  \
                      dim3(EM_THREADS), lds, stream, a, widx,              \
                      reinterpret_cast<const uint16_t*>(dout), part, B, T, \
                      S);                                                  \
@@ -311,10 +328,10 @@ void launch_embed_onehot_partials(const EmbedBwdArgs& a, int32_t n,
                                   const int32_t* widx, const void* dout,
                                   float* part, int64_t B, int32_t T,
                                   int32_t D, int32_t S, int32_t nslab,
-                                  hipStream_t stream) {
-  const size_t lds = (size_t)S * 4 + (size_t)D * (S + 8) * 2;
+                                  int32_t nslice, hipStream_t stream) {
+  const size_t lds = (size_t)S * 4 + (size_t)(D / nslice) * (S + 8) * 2;
 #define EM_PARTIALS(W)                                                    \
-  hipLaunchKernelGGL(embed_bwd_onehot_kernel<W>, dim3(n, nslab),          \
+  hipLaunchKernelGGL(embed_bwd_onehot_kernel<W>, dim3(n, nslab, nslice),  \
                      dim3(EM_THREADS), lds, stream, a, widx,              \
                      reinterpret_cast<const uint16_t*>(dout), part, B, T, \
                      S)

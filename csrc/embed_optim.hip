@@ -8,8 +8,9 @@
 //   adagrad          h' = h + g * g                       (per element)
 //                    p' = p - lr * (g / (sqrt(h') + eps))
 //   rowwise_adagrad  s_l = ((gx*gx + gy*gy) + gz*gz) + gw*gw   per lane
-//                    s   = xor-butterfly sum of s_l over the row's D/4
-//                          lanes, distances 1, 2, 4
+//                    s   = xor-butterfly sum of s_l over the row's
+//                          G = D/4 lanes, distances 1 .. G/2 ascending
+//                          (1, 2, 4 at D = 32; 1 .. 16 at D = 128)
 //                    h' = h + s * (1/D)                   (one float per row)
 //                    p' = p - lr * (g / (sqrt(h') + eps))
 //
@@ -120,6 +121,11 @@ template <int D>
 __device__ __forceinline__ float eo_row_state(const float4 g, float h) {
   #pragma clang fp contract(off)
   constexpr int G = D / 4;
+  // __shfl_xor's width: a power of two inside one wave, and the groups
+  // tile the workgroup, so a group never straddles two waves.
+  static_assert(G >= 2 && G <= 32 && (G & (G - 1)) == 0 &&
+                    EM_THREADS % G == 0,
+                "a row's lanes are a power-of-two group of at most 32");
   const float xx = g.x * g.x;
   const float yy = g.y * g.y;
   const float zz = g.z * g.z;
@@ -323,6 +329,12 @@ EMBED_KERNEL void __launch_bounds__(EM_THREADS)
     case 16 * 4 + 2: { CALL(16, 2); break; }          \
     case 32 * 4 + 0: { CALL(32, 0); break; }          \
     case 32 * 4 + 1: { CALL(32, 1); break; }          \
+    case 64 * 4 + 0: { CALL(64, 0); break; }          \
+    case 64 * 4 + 1: { CALL(64, 1); break; }          \
+    case 64 * 4 + 2: { CALL(64, 2); break; }          \
+    case 128 * 4 + 0: { CALL(128, 0); break; }        \
+    case 128 * 4 + 1: { CALL(128, 1); break; }        \
+    case 128 * 4 + 2: { CALL(128, 2); break; }        \
     default: { CALL(32, 2); break; }                  \
   }
 

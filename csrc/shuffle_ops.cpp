@@ -1922,9 +1922,14 @@ void eval_accumulate(const at::Tensor& part, const at::Tensor& acc,
 
 namespace {
 
+// The widths csrc/embed.hip and csrc/embed_optim.hip are instantiated at.
+bool embed_width_ok(int64_t D) {
+  return D == 8 || D == 16 || D == 32 || D == 64 || D == 128;
+}
+
 void check_embed_dout(const at::Tensor& dout, const at::Tensor& widx,
                       const at::Tensor& grad, int64_t D, const char* who) {
-  TORCH_CHECK(D == 8 || D == 16 || D == 32, who, ": D must be 8, 16 or 32");
+  TORCH_CHECK(embed_width_ok(D), who, ": D must be 8, 16, 32, 64 or 128");
   TORCH_CHECK(widx.is_cuda() && widx.scalar_type() == at::kInt &&
                   widx.dim() == 2 && widx.is_contiguous() &&
                   widx.size(0) >= 1 && widx.size(1) >= 1 &&
@@ -1948,7 +1953,8 @@ void check_embed_dout(const at::Tensor& dout, const at::Tensor& widx,
 }
 
 // Rows of a batch slab of the one-hot regime: at least 64 slabs per table
-// where the batch allows, 256 rows or more each, at most what the LDS holds.
+// where the batch allows, 256 rows or more each, at most what the LDS holds
+// (a slice of at most 32 columns: 512 rows from D = 32 up).
 int64_t embed_slab_rows(int64_t B, int64_t D) {
   const int64_t S = (((B + 63) / 64) + 15) / 16 * 16;
   return std::min<int64_t>(embed_max_slab((int32_t)D),
@@ -2014,8 +2020,8 @@ std::tuple<at::Tensor, at::Tensor> embed_concat_fwd(
   TORCH_CHECK((int64_t)indices.size() == T,
               "embed_concat_fwd: one index tensor per table");
   const int64_t D = tables[0].dim() == 2 ? tables[0].size(1) : 0;
-  TORCH_CHECK(D == 8 || D == 16 || D == 32,
-              "embed_concat_fwd: D must be 8, 16 or 32");
+  TORCH_CHECK(embed_width_ok(D),
+              "embed_concat_fwd: D must be 8, 16, 32, 64 or 128");
   const int64_t B = indices[0].size(0);
   TORCH_CHECK(B >= 1, "embed_concat_fwd: B must be at least 1");
   const auto dev = tables[0].get_device();
@@ -2085,6 +2091,8 @@ void embed_bwd_onehot(const at::Tensor& dout, const at::Tensor& widx,
     a.card[i] = (int32_t)cards[i];
     a.row_off[i] = row_offs[i];
     a.part_off[i] = part_floats;
+    // [nslab, card_pad, D]: the D / 32 column slices of a wide table write
+    // side by side into the same rows
     part_floats += nslab * ((cards[i] + 31) / 32 * 32) * D;
     max_card = std::max(max_card, cards[i]);
   }
@@ -2092,7 +2100,8 @@ void embed_bwd_onehot(const at::Tensor& dout, const at::Tensor& widx,
   launch_embed_bwd_onehot(a, (int32_t)n, widx.data_ptr<int32_t>(),
                           dout.data_ptr(), part.data_ptr<float>(),
                           grad.data_ptr<float>(), B, (int32_t)T, (int32_t)D,
-                          (int32_t)S, (int32_t)nslab, (int32_t)max_card,
+                          (int32_t)S, (int32_t)nslab,
+                          embed_slices((int32_t)D), (int32_t)max_card,
                           current_stream());
 }
 
@@ -2170,7 +2179,8 @@ void embed_onehot_update(const at::Tensor& dout, const at::Tensor& widx,
   launch_embed_onehot_partials(a, (int32_t)n, widx.data_ptr<int32_t>(),
                                dout.data_ptr(), part.data_ptr<float>(), B,
                                (int32_t)T, (int32_t)D, (int32_t)S,
-                               (int32_t)nslab, current_stream());
+                               (int32_t)nslab, embed_slices((int32_t)D),
+                               current_stream());
   launch_embed_fold_update(o, (int32_t)n, part.data_ptr<float>(), (int32_t)D,
                            (int32_t)nslab, (int32_t)max_card,
                            current_stream());
@@ -2369,6 +2379,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kind"), py::arg("lr"), py::arg("eps"));
   // embed_onehot_update / embed_runs_update
   m.attr("EMBED_OPTIM") = 1;
+  // D = 64 and 128 in every embed_* binding
+  m.attr("EMBED_WIDE") = 1;
   m.attr("EMBED_SGD") = (int)rsdl::kEmbedSgd;
   m.attr("EMBED_ADAGRAD") = (int)rsdl::kEmbedAdagrad;
   m.attr("EMBED_ROWWISE_ADAGRAD") = (int)rsdl::kEmbedRowwiseAdagrad;

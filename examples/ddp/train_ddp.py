@@ -99,6 +99,10 @@ def parse_args(argv=None):
                    "lookups and the concat as one HIP launch with a "
                    "deterministic backward "
                    "(models.fused_embedding.fused_embedding)")
+    p.add_argument("--embed-dim", type=int, default=16,
+                   help="EmbeddingMLP path (--spec tabular): width of every "
+                   "embedding table. --fused-embedding runs in HIP at 8, "
+                   "16, 32, 64 and 128")
     p.add_argument("--embedding-optimizer",
                    choices=["torch", "sgd", "adagrad", "rowwise-adagrad"],
                    default="torch",
@@ -256,7 +260,8 @@ def train_main(args, world, rank):
                 kind=args.embedding_optimizer.replace("-", "_"), lr=args.lr,
             )
         model = EmbeddingMLP(
-            cardinalities, fused_embedding=args.fused_embedding,
+            cardinalities, embed_dim=args.embed_dim,
+            fused_embedding=args.fused_embedding,
             embedding_optimizer=embed_opt,
         ).to(device)
         embed_opt = model.embedding_optimizer

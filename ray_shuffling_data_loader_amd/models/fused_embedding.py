@@ -20,10 +20,15 @@ The T gradients are views of one flat zero-initialised fp32 buffer and are
 returned as ordinary dense gradients, so any torch optimizer and DDP keep
 working. The tables stay separate fp32 ``nn.Embedding.weight`` parameters.
 
-On CPU tensors, or for an input the kernels do not serve (D outside
-{8, 16, 32}, more than 64 tables, non-fp32 tables, B = 0), the same
-arithmetic runs as torch ops: gather, cast and cat forward, an fp32
-``index_add_`` of the bf16 gradients backward (ascending batch row on CPU).
+The kernels serve D in {8, 16, 32, 64, 128}. At 64 and 128 the one-hot
+product is cut into 32-column slices, one workgroup each, so its slab stays
+at the 512 rows of D = 32; these two widths need an extension with
+``EMBED_WIDE``.
+
+On CPU tensors, or for an input the kernels do not serve (any other D, more
+than 64 tables, non-fp32 tables, B = 0), the same arithmetic runs as torch
+ops: gather, cast and cat forward, an fp32 ``index_add_`` of the bf16
+gradients backward (ascending batch row on CPU).
 
 ``fused_embedding(indices, tables, optimizer=opt)`` with a
 ``FusedEmbeddingOptimizer`` leaves the dense gradients out altogether: the
@@ -46,6 +51,8 @@ _DENSE_MAX_ROWS = int(os.environ.get("RSDL_EMBED_DENSE_MAX", "256") or "256")
 
 _MAX_TABLES = 64
 _WIDTHS = (8, 16, 32)
+# served as well once the loaded extension has EMBED_WIDE (_width_served)
+_WIDE_WIDTHS = (64, 128)
 
 # (device, cards, large) -> (table numbers, row offsets) of the sorted regime
 _KEY_CACHE = {}
@@ -69,13 +76,25 @@ def _split(indices, T):
     return indices
 
 
+def _width_served(D) -> bool:
+    """D is a width the loaded extension has kernels for: 64 and 128 came
+    with ``EMBED_WIDE``, and a build from before it keeps the torch ops."""
+    if D in _WIDTHS:
+        return True
+    if D not in _WIDE_WIDTHS:
+        return False
+    from ray_shuffling_data_loader_amd.ops import shuffle_ops
+
+    return bool(getattr(shuffle_ops._load_hip(), "EMBED_WIDE", 0))
+
+
 def _kernels_serve(idx, tables) -> bool:
     T = len(tables)
     w0 = tables[0]
     if not (1 <= T <= _MAX_TABLES) or not w0.is_cuda or w0.dim() != 2:
         return False
     D, B = w0.shape[1], idx[0].shape[0]
-    if D not in _WIDTHS or B < 1:
+    if B < 1 or not _width_served(D):
         return False
     rows = 0
     for w, x in zip(tables, idx):
@@ -257,8 +276,8 @@ class FusedEmbeddingOptimizer:
       adagrad          h' = h + g * g                       (per element)
                        p' = p - lr * (g / (sqrt(h') + eps))
       rowwise_adagrad  s_l = ((gx*gx + gy*gy) + gz*gz) + gw*gw  per 4 elements
-                       s   = xor-butterfly sum of the D/4 s_l, distances
-                             1, 2, 4
+                       s   = xor-butterfly sum of the G = D/4 s_l, distances
+                             1 .. G/2 ascending (1, 2, 4, 8, 16 at D = 128)
                        h' = h + s * (1/D)                   (one per row)
                        p' = p - lr * (g / (sqrt(h') + eps))
 
@@ -504,7 +523,8 @@ def fused_embedding(indices, tables, optimizer=None) -> torch.Tensor:
 
     ``indices``: T int64 tensors [B] or [B,1] with any row stride (column
     views of a packed batch are read in place), or one [B,T] matrix.
-    ``tables``: T fp32 [card_t, D] tensors, e.g. ``nn.Embedding.weight``.
+    ``tables``: T fp32 [card_t, D] tensors, e.g. ``nn.Embedding.weight``;
+    D in {8, 16, 32, 64, 128} runs in HIP on GPU tensors.
     ``optimizer``: a ``FusedEmbeddingOptimizer`` bound to these tables; the
     backward then gives them no ``.grad`` and ``optimizer.step()`` applies
     the batch."""

@@ -240,8 +240,9 @@ class EmbeddingMLP(nn.Module):
     (the realistic counterpart of the reference example's unused Net).
 
     ``fused_embedding=True`` runs the lookups and the concat as one HIP
-    launch with a deterministic backward (models/fused_embedding.py);
-    parameter names and shapes are the same either way.
+    launch with a deterministic backward (models/fused_embedding.py) for
+    ``embed_dim`` 8, 16, 32, 64 or 128; parameter names and shapes are the
+    same either way.
 
     ``embedding_optimizer`` (with ``fused_embedding=True``) is passed
     through as ``fused_embedding(optimizer=)``: the tables then get no
