@@ -100,21 +100,10 @@ __device__ __forceinline__ T _rsdl_load(const T* p) {
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short fc_bf16x8;
 typedef __attribute__((__vector_size__(16 * sizeof(float)))) float fc_f32x16;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int fc_u32x4;
 typedef __attribute__((__vector_size__(2 * sizeof(unsigned int)))) unsigned int fc_u32x2;
-typedef __attribute__((__vector_size__(2 * sizeof(float)))) float fc_f32x2;
-
-// Packed pair helpers (one VALU op per TWO elements on gfx950).
-__device__ __forceinline__ fc_f32x2 fc_pk_max0(fc_f32x2 v) {
-  // no packed f32 max on gfx950; two v_max_f32
-  fc_f32x2 r = {fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)};
-  return r;
-}
-__device__ __forceinline__ uint32_t fc_cvt_pk_bf16(fc_f32x2 v) {
-  uint32_t p;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(v[0]), "v"(v[1]));
-  return p;
-}
+// fc_f32x2, fc_u32x4 and the packed pair helpers of the epilogue (one VALU
+// op per TWO elements on gfx950) live in chain.h, shared with the wgrad
+// body that recomputes a1.
 
 #define FC_MT 32            // rows per MFMA m-tile (and per x/mask block)
 #define FC_K0 100           // input feature count
@@ -169,6 +158,10 @@ __device__ __forceinline__ short fc_f2b(float f) {
 // one uniform flag — no per-element guards in the loops.
 // SYNC_EPI: a workgroup barrier between the k-loop and the epilogue, for
 // a dst tile that aliases the src tile.
+// EMIT_A (with EMIT_T): off keeps the mask words and drops the transposed
+// activation fragments, exchange and 16-byte stores included; at_out is
+// then never touched. For layer 1 of the train step when the dW2 wgrad
+// recomputes a1 from x and W1 itself (csrc/wgrad_frag.hip).
 // __forceinline__: the chain kernels are instantiated once per loss /
 // task, so each emitting layer has more than one caller; left to its cost
 // model the compiler then keeps the layers out-of-line, and the 64-row
@@ -176,7 +169,7 @@ __device__ __forceinline__ short fc_f2b(float f) {
 // Inlined, every instantiation has the single-caller figures.
 template <int K, int N, int MPW, int NT, int SRC_S, int DST_S, bool RELU,
           bool A_FRAGMAJOR = false, bool EMIT_T = false, bool PI16 = false,
-          bool SYNC_EPI = false>
+          bool SYNC_EPI = false, bool EMIT_A = true>
 __device__ __forceinline__ void fc_layer(
     const short* __restrict__ src_lds, const short* __restrict__ W,
     const float* __restrict__ bias, short* __restrict__ dst_lds,
@@ -273,10 +266,8 @@ __device__ __forceinline__ void fc_layer(
       #pragma unroll
       for (int q = 0; q < 8; q++) {
         const int32_t roff = (((2 * q) & 3) + 8 * (q >> 1)) * DST_S;
-        fc_f32x2 v2 = {acc[mt][nt][2 * q], acc[mt][nt][2 * q + 1]};
-        v2 += bv2;
-        if (RELU) v2 = fc_pk_max0(v2);
-        const uint32_t pk = fc_cvt_pk_bf16(v2);
+        const uint32_t pk = fc_epi_pair<RELU>(
+            acc[mt][nt][2 * q], acc[mt][nt][2 * q + 1], bv2);
         p[q] = pk;
         colbase[roff] = (short)(pk & 0xFFFFu);
         colbase[roff + DST_S] = (short)(pk >> 16);
@@ -302,39 +293,26 @@ __device__ __forceinline__ void fc_layer(
         // Default (!PI16): exchange the half-rows as packed ints (4
         // shfls); lane h=0 assembles rows {0-7},{16-23}, h=1
         // {8-15},{24-31}.
-        fc_u32x4 run0, run1;
-        if (PI16) {
-          #pragma unroll
-          for (int j = 0; j < 4; j++) {
-            run0[j] = p[j];
-            run1[j] = p[4 + j];
+        if (EMIT_A) {
+          fc_u32x4 run0, run1;
+          if (PI16) {
+            #pragma unroll
+            for (int j = 0; j < 4; j++) {
+              run0[j] = p[j];
+              run1[j] = p[4 + j];
+            }
+          } else {
+            fc_half_row_exchange(p, h, run0, run1);
           }
-        } else {
-          uint32_t rx[4];
-          #pragma unroll
-          for (int j = 0; j < 2; j++) {
-            rx[j] = __shfl_xor((int)(h == 0 ? p[2 + j] : p[j]), 32);
-            rx[2 + j] = __shfl_xor((int)(h == 0 ? p[6 + j] : p[4 + j]), 32);
-          }
-          run0[0] = h == 0 ? p[0] : rx[0];
-          run0[1] = h == 0 ? p[1] : rx[1];
-          run0[2] = h == 0 ? rx[0] : p[2];
-          run0[3] = h == 0 ? rx[1] : p[3];
-          run1[0] = h == 0 ? p[4] : rx[2];
-          run1[1] = h == 0 ? p[5] : rx[3];
-          run1[2] = h == 0 ? rx[2] : p[6];
-          run1[3] = h == 0 ? rx[3] : p[7];
+          const int64_t nt_g = (int64_t)(n_base + nt * 32) >> 5;
+          const int64_t mc = mc0 + 2 * (mt0 + mt);
+          short* blk0 = at_out + ((nt_g * mchunks + mc) * 512) + h * 256 +
+                        ml * 8;
+          short* blk1 = at_out + ((nt_g * mchunks + mc + 1) * 512) +
+                        h * 256 + ml * 8;
+          _rsdl_store(run0, reinterpret_cast<fc_u32x4*>(blk0));
+          _rsdl_store(run1, reinterpret_cast<fc_u32x4*>(blk1));
         }
-        const int64_t nt_g = (int64_t)(n_base + nt * 32) >> 5;
-        const int64_t mc = mc0 + 2 * (mt0 + mt);
-        short* blk0 = at_out + ((nt_g * mchunks + mc) * 512) + h * 256 +
-                      ml * 8;
-        short* blk1 = at_out + ((nt_g * mchunks + mc + 1) * 512) +
-                      h * 256 + ml * 8;
-        _rsdl_store(run0,
-                                    reinterpret_cast<fc_u32x4*>(blk0));
-        _rsdl_store(run1,
-                                    reinterpret_cast<fc_u32x4*>(blk1));
         w |= __shfl_xor(w, 32);
         if (h == 0) mask_row[(mt0 + mt) * N + n] = w;
       }
@@ -427,7 +405,11 @@ __device__ __forceinline__ int32_t fc_fresh_lane(int32_t lane) {
 // p t (1-sg), 1-sg taken as sigmoid(-o). The grouping makes w = 1, p = 1
 // reproduce the unweighted bits; a row with w = 0 gives dyb = +-0 and a
 // zero term.
-template <int MT, bool PI16, int LOSS, bool WEIGHTED>
+// EMIT_A1 = false (fwd_chain_kernel<.., false>, 64-row slabs without PI16
+// only): layer 1 writes its LDS tile and mask words but no a1^T, which is
+// then never dereferenced (null) — the dW2 wgrad recomputes a1. Every other
+// output is bit for bit that of the emitting instantiation.
+template <int MT, bool PI16, int LOSS, bool WEIGHTED, bool EMIT_A1 = true>
 __device__ __forceinline__ void fc_fwd_chain_body(
     const short* __restrict__ x0s,  // fragment-major swizzled x (see note)
     const short* __restrict__ W1, const float* __restrict__ b1,
@@ -482,7 +464,8 @@ __device__ __forceinline__ void fc_fwd_chain_body(
   // Layer 1: A fragments straight from the swizzled global x block.
   const short* xblk = &x0s[mt_g0 * (FC_K0P / 16) * 512];
   constexpr int NT1 = FC_N1 / (128 * MT), NT2 = FC_N2 / (128 * MT);
-  fc_layer<FC_K0P, FC_N1, MT, NT1, 0, FC_S1, true, true, true, PI16>(
+  fc_layer<FC_K0P, FC_N1, MT, NT1, 0, FC_S1, true, true, true, PI16, false,
+           EMIT_A1>(
       xblk, W1, b1, t1, 0, wave * NT1, fc_fresh_lane<MT>(lane), has2, a1t,
       &mask1[mt_g0 * FC_N1], mchunks, mc0);
   __syncthreads();
@@ -571,7 +554,7 @@ __device__ __forceinline__ void fc_fwd_chain_body(
 
 // The one entry point per instantiation. ``weight`` and ``pos_weight`` are
 // always in the argument list; the WEIGHTED = false body never reads them.
-template <int MT, bool PI16, int LOSS, bool WEIGHTED>
+template <int MT, bool PI16, int LOSS, bool WEIGHTED, bool EMIT_A1 = true>
 __global__ void __launch_bounds__(256 * MT, MT == 2 ? 4 : 1)
 fwd_chain_kernel(
     const short* __restrict__ x0s, const short* __restrict__ W1,
@@ -585,7 +568,7 @@ fwd_chain_kernel(
     short* __restrict__ dyb, float* __restrict__ loss_part, float inv_m,
     int64_t M, int64_t mchunks, const float* __restrict__ weight,
     float pos_weight) {
-  fc_fwd_chain_body<MT, PI16, LOSS, WEIGHTED>(
+  fc_fwd_chain_body<MT, PI16, LOSS, WEIGHTED, EMIT_A1>(
       x0s, W1, b1, W2, b2, W3, b3, w4, b4, a1t, mask1, a2t, mask2, a3, out,
       target, dyb, loss_part, inv_m, M, mchunks, weight, pos_weight);
 }
@@ -983,12 +966,24 @@ static auto fwd_chain_pick(int pi16, int loss, bool weighted) {
               : fwd_chain_pick<MT, false>(loss, weighted);
 }
 
+// The instantiations without the a1^T emission: 64-row slabs, PI16 off.
+static auto fwd_chain_pick_noemit(int loss, bool weighted) {
+  if (loss == FC_LOSS_BCE) {
+    return weighted ? fwd_chain_kernel<2, false, FC_LOSS_BCE, true, false>
+                    : fwd_chain_kernel<2, false, FC_LOSS_BCE, false, false>;
+  }
+  return weighted ? fwd_chain_kernel<2, false, FC_LOSS_MSE, true, false>
+                  : fwd_chain_kernel<2, false, FC_LOSS_MSE, false, false>;
+}
+
 void launch_fwd_chain(const FwdChainArgs& p, hipStream_t stream) {
   const int32_t grid = (int32_t)fwd_chain_grid(p.M, p.rows);
   // The global layouts are per 32-row m-tile whatever the slab size.
   const int64_t mchunks = (p.M + FC_MT - 1) / FC_MT * 2;
   auto kern = p.rows == 64 ? fwd_chain_pick<2>(p.pi16, p.loss, p.weighted)
                            : fwd_chain_pick<1>(p.pi16, p.loss, p.weighted);
+  // No a1^T (the binding asks for it at 64 rows without pi16 only).
+  if (p.a1t == nullptr) kern = fwd_chain_pick_noemit(p.loss, p.weighted);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(p.rows == 64 ? 512 : 256), 0,
                      stream,
                      reinterpret_cast<const short*>(p.x0s),

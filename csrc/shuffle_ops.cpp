@@ -954,8 +954,11 @@ static HeadWeights head_weights(const char* who, const at::Tensor& x,
 // fused_step_bf16. Weights arrive fragment-major (W1 with K padded to
 // 112), biases fp32, ``tgt`` fp32 [M] or nullptr. Nothing is launched for
 // M == 0 (the weight tensors may then be undefined).
+// ``xs`` is the fragment-major x the chain read (undefined at M == 0).
+// With ``emit_a1`` false (rows = 64 without pi16 only) layer 1 emits no
+// a1^T and ``a1t`` is an empty tensor: the dW2 wgrad recomputes a1 from xs.
 struct FwdChainOut {
-  at::Tensor a1t, mask1, a2t, mask2, a3, out, dyb, loss_part;
+  at::Tensor a1t, mask1, a2t, mask2, a3, out, dyb, loss_part, xs;
 };
 
 FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
@@ -965,7 +968,10 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
                           const at::Tensor& b4f, const at::Tensor* tgt,
                           const c10::optional<at::Tensor>& xt_out,
                           bool pi16, int rows, int loss,
-                          const HeadWeights& hw = HeadWeights()) {
+                          const HeadWeights& hw = HeadWeights(),
+                          bool emit_a1 = true) {
+  TORCH_CHECK(emit_a1 || (rows == 64 && !pi16),
+              "fwd_chain: emit_a1=false needs rows=64 and pi16 off");
   FwdChainOut f;
   const int64_t M = x.size(0);
   // a1/a2 exist only TRANSPOSED in wgrad fragment-major layout (plus
@@ -974,7 +980,7 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
   // row-major a1/a2.
   const int64_t mtiles = std::max<int64_t>((M + 31) / 32, 1);
   const int64_t mchunks = mtiles * 2;
-  f.a1t = at::empty({16 * mchunks * 512}, x.options());
+  f.a1t = at::empty({emit_a1 ? 16 * mchunks * 512 : 0}, x.options());
   f.a2t = at::empty({8 * mchunks * 512}, x.options());
   f.mask1 = at::empty({mtiles, 512}, x.options().dtype(at::kInt));
   f.mask2 = at::empty({mtiles, 256}, x.options().dtype(at::kInt));
@@ -1006,11 +1012,12 @@ FwdChainOut run_fwd_chain(const at::Tensor& x, const at::Tensor& W1s,
     } else {
       launch_swizzle_x(x.data_ptr(), xs.data_ptr(), M, current_stream());
     }
+    f.xs = xs;
     p.x0s = xs.data_ptr();
     p.w = {W1s.data_ptr(), b1f.data_ptr<float>(), W2s.data_ptr(),
            b2f.data_ptr<float>(), W3s.data_ptr(), b3f.data_ptr<float>(),
            w4.data_ptr(), b4f.data_ptr<float>()};
-    p.a1t = f.a1t.data_ptr();
+    p.a1t = emit_a1 ? f.a1t.data_ptr() : nullptr;
     p.mask1 = reinterpret_cast<uint32_t*>(f.mask1.data_ptr<int32_t>());
     p.a2t = f.a2t.data_ptr();
     p.mask2 = reinterpret_cast<uint32_t*>(f.mask2.data_ptr<int32_t>());
@@ -1036,7 +1043,7 @@ std::vector<at::Tensor> fwd_chain_bf16(
     const c10::optional<at::Tensor>& target,
     const c10::optional<at::Tensor>& xt_out, bool pi16, int64_t rows,
     int64_t loss, const c10::optional<at::Tensor>& weight,
-    double pos_weight) {
+    double pos_weight, bool emit_a1) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fwd_chain", "loss");
   // Sample weights / pos_weight of the loss epilogue (need a target).
@@ -1090,7 +1097,7 @@ std::vector<at::Tensor> fwd_chain_bf16(
   }
   auto f = run_fwd_chain(x, W1s, W2s, W3s, w4, b1f, b2f, b3f, b4f,
                          with_loss ? &tgt : nullptr, xt_out, pi16, crows,
-                         closs, hw);
+                         closs, hw, emit_a1);
   if (with_loss) {
     return {f.a1t, f.mask1, f.a2t, f.mask2, f.a3, f.out, f.dyb,
             f.loss_part};
@@ -1251,16 +1258,16 @@ at::Tensor run_wgrad_frag(const at::Tensor& AT, const at::Tensor& BT,
 std::vector<at::Tensor> run_wgrad_grouped(
     const at::Tensor& dz1t, const at::Tensor& xt, const at::Tensor& dz2t,
     const at::Tensor& a1t, const at::Tensor& dz3t, const at::Tensor& a2t,
-    int64_t mchunks) {
+    int64_t mchunks, const WgradRecompute* rc = nullptr) {
   const WgradGroupedSlabs ns = wgrad_grouped_nslabs(mchunks);
   auto f32 = dz1t.options().dtype(at::kFloat);
   auto p1 = at::empty({ns.ns[0], 512 * 128}, f32);
   auto p2 = at::empty({ns.ns[1], 256 * 512}, f32);
   auto p3 = at::empty({ns.ns[2], 128 * 256}, f32);
   launch_wgrad_grouped(dz1t.data_ptr(), xt.data_ptr(), p1.data_ptr<float>(),
-                       dz2t.data_ptr(), a1t.data_ptr(), p2.data_ptr<float>(),
-                       dz3t.data_ptr(), a2t.data_ptr(), p3.data_ptr<float>(),
-                       mchunks, current_stream());
+                       dz2t.data_ptr(), rc ? nullptr : a1t.data_ptr(),
+                       p2.data_ptr<float>(), dz3t.data_ptr(), a2t.data_ptr(),
+                       p3.data_ptr<float>(), mchunks, rc, current_stream());
   return {p1, p2, p3};
 }
 
@@ -1351,6 +1358,46 @@ std::vector<at::Tensor> wgrad_grouped_partials_bf16(
   check_wgrad_frag(dz2t, a1t, 256, 512, mchunks, 1, 8, 0);
   check_wgrad_frag(dz3t, a2t, 128, 256, mchunks, 1, 8, 0);
   return run_wgrad_grouped(dz1t, xt, dz2t, a1t, dz3t, a2t, mchunks);
+}
+
+// The dW2 partials [ns2, 256*512] of the grouped launch's slabs from the
+// recompute body alone (csrc/wgrad_frag.hip, wgrad_rc_kernel): a1 =
+// relu(x W1^T + b1) is formed in the kernel from ``xs`` (fragment-major x,
+// [mchunks/2][7][2][32][8], pads zero), ``W1s`` (fragment-major W1
+// [512,112]) and ``b1`` (fp32 [512]), bit for bit what fwd_chain_bf16 emits
+// as a1^T, and contracted with ``dz2t``. Equal, bit for bit, to part2 of
+// wgrad_grouped_partials_bf16 fed that a1^T.
+at::Tensor wgrad_recompute_partials_bf16(const at::Tensor& xs,
+                                         const at::Tensor& W1s,
+                                         const at::Tensor& b1,
+                                         const at::Tensor& dz2t,
+                                         int64_t mchunks) {
+  TORCH_CHECK(mchunks > 0 && mchunks % 2 == 0,
+              "wgrad_recompute_partials: mchunks must be positive and even");
+  auto bf16 = [&](const at::Tensor& t, int64_t n, const char* nm) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                    t.is_contiguous() && t.numel() == n &&
+                    t.get_device() == dz2t.get_device() &&
+                    reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                "wgrad_recompute_partials: ", nm,
+                " must be contiguous aligned bf16 with ", n,
+                " elements on one GPU (numel ", t.numel(), ")");
+  };
+  bf16(dz2t, 8 * mchunks * 512, "dz2t");
+  bf16(xs, (mchunks / 2) * 7 * 512, "xs");
+  bf16(W1s, 512 * 112, "W1s");
+  TORCH_CHECK(b1.is_cuda() && b1.scalar_type() == at::kFloat &&
+                  b1.is_contiguous() && b1.numel() == 512 &&
+                  b1.get_device() == dz2t.get_device(),
+              "wgrad_recompute_partials: b1 must be contiguous fp32 [512] on "
+              "dz2t's GPU");
+  const int64_t ns = wgrad_grouped_nslabs(mchunks).ns[1];
+  auto part = at::empty({ns, 256 * 512}, dz2t.options().dtype(at::kFloat));
+  const WgradRecompute rc{xs.data_ptr(), W1s.data_ptr(),
+                          b1.data_ptr<float>()};
+  launch_wgrad_recompute(rc, dz2t.data_ptr(), part.data_ptr<float>(), mchunks,
+                         current_stream());
+  return part;
 }
 
 // ---------------------------------------------------------------------
@@ -1699,7 +1746,7 @@ std::vector<at::Tensor> fused_step_bf16(
     const c10::optional<std::vector<at::Tensor>>& outs, int64_t rows,
     int64_t loss, const c10::optional<at::Tensor>& weight,
     double pos_weight, int64_t wgrad_variant, int64_t wgrad_grouped,
-    const c10::optional<StepOpt>& opt) {
+    const c10::optional<StepOpt>& opt, int64_t wgrad_recompute) {
   const int crows = chain_rows(rows);
   const int closs = chain_loss(loss, "fused_step", "loss");
   TORCH_CHECK(wgrad_variant >= 0 && wgrad_variant <= 2,
@@ -1710,6 +1757,9 @@ std::vector<at::Tensor> fused_step_bf16(
               wgrad_grouped);
   TORCH_CHECK(wgrad_grouped != 1 || wgrad_variant == 0,
               "fused_step: wgrad_grouped=1 needs wgrad_variant 0");
+  TORCH_CHECK(wgrad_recompute >= -1 && wgrad_recompute <= 1,
+              "fused_step: wgrad_recompute must be -1 (default), 0 or 1, "
+              "got ", wgrad_recompute);
   const HeadWeights hw =
       head_weights("fused_step", x, weight, pos_weight, closs);
   check_x("fused_step", x);
@@ -1742,9 +1792,27 @@ std::vector<at::Tensor> fused_step_bf16(
   const int64_t mchunks = 2 * ((M + 31) / 32);
   c10::optional<at::Tensor> xt =
       at::empty({4 * mchunks * 512}, x.options());
+  // At variant 0 the three wgrads are one grouped launch, unless
+  // RSDL_WGRAD_GROUPED=0 or a tuning knob of the separate launches asks
+  // for those (wgrad_grouped_default); wgrad_grouped 0 / 1 decides it for
+  // this call. Only the slab partition, so the grouping of the fp32 sums
+  // of dW1-dW3, differs between the two.
+  const bool grouped =
+      wgrad_variant == 0 &&
+      (wgrad_grouped < 0 ? wgrad_grouped_default() : wgrad_grouped == 1);
+  // With the grouped launch, 64-row slabs and no pi16 the forward emits no
+  // a1^T (never allocated) and the dW2 workgroups recompute a1 from the
+  // fragment-major x and W1 instead: the same bits everywhere, 512 MB less
+  // HBM traffic at M = 250k. RSDL_WGRAD_RECOMPUTE=0 (wgrad_recompute_default)
+  // or wgrad_recompute 0 keeps the emitting pair; anywhere else the knob
+  // has no effect.
+  const bool recompute =
+      grouped && crows == 64 && !pi16 &&
+      (wgrad_recompute < 0 ? wgrad_recompute_default()
+                           : wgrad_recompute == 1);
   auto f = run_fwd_chain(x, pr.W1s, pr.W2s, pr.W3s, pr.w4b, biases[0],
                          biases[1], biases[2], biases[3], &pr.tgt, xt, pi16,
-                         crows, closs, hw);
+                         crows, closs, hw, !recompute);
   auto b = run_bwd_chain(f.dyb, f.a3, f.mask1, f.mask2, pr.w4b, pr.W3Ts,
                          pr.W2Ts, pi16, crows);
   // Same tile-config choice as ops.shuffle_ops.wgrad_frag.
@@ -1754,15 +1822,11 @@ std::vector<at::Tensor> fused_step_bf16(
   // launch_wgrad_frag. The small tiles have the direct kernel only, and
   // the launcher keeps them on it whatever the variant.
   const int64_t wv = wgrad_variant;  // 0 | 1 | 2, checked above
-  // At variant 0 the three wgrads are one grouped launch, unless
-  // RSDL_WGRAD_GROUPED=0 or a tuning knob of the separate launches asks
-  // for those (wgrad_grouped_default); wgrad_grouped 0 / 1 decides it for
-  // this call. Only the slab partition, so the grouping of the fp32 sums
-  // of dW1-dW3, differs between the two.
-  if (wv == 0 &&
-      (wgrad_grouped < 0 ? wgrad_grouped_default() : wgrad_grouped == 1)) {
+  if (grouped) {
+    const WgradRecompute rc{f.xs.data_ptr(), pr.W1s.data_ptr(),
+                            biases[0].data_ptr<float>()};
     auto p = run_wgrad_grouped(b.dz1t, *xt, b.dz2t, f.a1t, b.dz3t, f.a2t,
-                               mchunks);
+                               mchunks, recompute ? &rc : nullptr);
     return finalize(p[0], p[1], p[2], b.db_part, f.loss_part);
   }
   auto p1 = run_wgrad_frag(b.dz1t, *xt, 512, 128, mchunks, 2, 4, wv);
@@ -2323,7 +2387,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("target") = c10::nullopt,
         py::arg("xt_out") = c10::nullopt, py::arg("pi16") = false,
         py::arg("rows") = 0, py::arg("loss") = 0,
-        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0);
+        py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0,
+        py::arg("emit_a1") = true);
   m.def("bwd_chain_bf16", &rsdl::bwd_chain_bf16, py::arg("dy"),
         py::arg("a3"), py::arg("mask1"), py::arg("mask2"), py::arg("w4"),
         py::arg("W3"), py::arg("W2"), py::arg("pi16") = false,
@@ -2339,7 +2404,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows") = 0, py::arg("loss") = 0,
         py::arg("weight") = c10::nullopt, py::arg("pos_weight") = 1.0,
         py::arg("wgrad_variant") = 0, py::arg("wgrad_grouped") = -1,
-        py::arg("opt") = c10::nullopt);
+        py::arg("opt") = c10::nullopt, py::arg("wgrad_recompute") = -1);
   m.def("step_finalize_update", &rsdl::step_finalize_update,
         py::arg("part1"), py::arg("part2"), py::arg("part3"),
         py::arg("db_part"), py::arg("loss_part"), py::arg("M"),
@@ -2352,6 +2417,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_grouped_partials_bf16", &rsdl::wgrad_grouped_partials_bf16,
         py::arg("dz1t"), py::arg("xt"), py::arg("dz2t"), py::arg("a1t"),
         py::arg("dz3t"), py::arg("a2t"), py::arg("mchunks"));
+  m.def("wgrad_recompute_partials_bf16",
+        &rsdl::wgrad_recompute_partials_bf16, py::arg("xs"), py::arg("W1s"),
+        py::arg("b1"), py::arg("dz2t"), py::arg("mchunks"));
   m.def("eval_chain_bf16", &rsdl::eval_chain_bf16, py::arg("x"),
         py::arg("Wstage"), py::arg("biases"),
         py::arg("target") = c10::nullopt, py::arg("pred_out") = c10::nullopt,

@@ -23,7 +23,9 @@
 // an LDS ring; the default for dW2 and dW3). launch_wgrad_frag picks:
 // explicit variant, then RSDL_WGRAD_LDS, then the per-shape default.
 // The train step runs its three wgrads as ONE launch of the ring body,
-// wgrad_grouped_kernel (launch_wgrad_grouped, at the end of the file).
+// wgrad_grouped_kernel (launch_wgrad_grouped, at the end of the file); by
+// default its dW2 workgroups run wgrad_rc_body instead, which recomputes
+// a1 from the forward's inputs so that a1^T never exists in HBM.
 //
 // Direct kernel: NO LDS, no barriers — per m-chunk (16 rows) each wave loads
 // its (NT_W + KT_W) fragments directly from global (coalesced; waves of
@@ -433,6 +435,250 @@ __device__ __forceinline__ void wgrad_lds_body(short* ring,
     }
   }
 }
+
+// ---------------------------------------------------------------------
+// dW2 with a1 recomputed: the forward chain then never writes a1^T
+// (256 MB at M = 250k, written once and read once) and this body reads
+// the forward's own inputs instead, the fragment-major x (56 MB) and W1.
+//
+// Block shape <2,4>: [256 n x 128 k], four workgroups per slab (one per
+// 128 columns of a1), the slab partition of the <1,8> ring body. The unit
+// of work is a PAIR of 16-row chunks, one 32-row m-tile of the forward:
+//   recompute(pair): wave w forms a1 n-tile kt0 + w of the m-tile exactly
+//     as fc_layer does (csrc/fwd_chain.hip): the x block's 7 k-chunks as A,
+//     its 7 W1 fragments (28 registers, loaded once) as B, the same
+//     v_mfma_f32_32x32x16_bf16 in ascending k from a zero accumulator, the
+//     shared epilogue (fc_epi_pair, fc_half_row_exchange; chain.h). run0 /
+//     run1 of the exchange ARE the two chunks' B fragments, bit for bit
+//     those the forward would have stored; the wave publishes them to a
+//     double-buffered LDS area that all four waves read.
+//   consume(pair): per chunk, in ascending order, every acc[nt][kt] gets
+//     one MFMA of its dz2^T fragment against the published fragment: the
+//     same products in the same chunk order as in wgrad_lds_body<1,8>, so
+//     the partials are bit-identical to the parent's at every shape.
+// A slab that starts or ends on an odd chunk recomputes the whole pair and
+// skips the MFMAs of the chunk outside it (workgroup-uniform), so the
+// partition needs no rounding; mchunks is even, so both chunks of every
+// pair exist.
+//
+// LDS (one object, 78 KB, two workgroups per CU): three 16 KB stages of
+// dz2^T (2 chunks x 8 fragments), two 7 KB x slots, two 8 KB publish
+// buffers. Per pair every wave issues 2 x DMAs, then 4 dz DMAs
+// (global_load_lds_dwordx4; wave 3 loads x fragment 6 twice so that the
+// counts are uniform). Iteration j, after ONE barrier: issue pair j + 2,
+// recompute pair j + 1, consume pair j. The wait ahead of the barrier
+// needs x of pair j + 1 and dz of pair j; vmcnt retires in order and x is
+// issued first, so the 4 dz DMAs of pair j + 1 stay in flight across it.
+constexpr int kRcDzStages = 3;
+constexpr int kRcDzStageElems = 16 * 512;
+constexpr int kRcXSlotElems = 7 * 512;
+constexpr int kRcPubElems = 8 * 512;
+constexpr int kRcXOff = kRcDzStages * kRcDzStageElems;
+constexpr int kRcPubOff = kRcXOff + 2 * kRcXSlotElems;
+constexpr int kRcRingElems = kRcPubOff + 2 * kRcPubElems;
+static_assert(2 * kRcRingElems * sizeof(short) <= 160 * 1024,
+              "two workgroups per CU");
+
+// The forward's inputs the recompute reads (device view of WgradRecompute).
+struct WgradRcSrc {
+  const short* xs;   // fragment-major x [mchunks / 2][7][2][32][8]
+  const short* W1s;  // fragment-major W1 [16][7][2][32][8]
+  const float* b1;   // [512]
+};
+
+__device__ __forceinline__ void wgrad_rc_body(short* ring,
+                                              const WgradProblem& p,
+                                              const WgradRcSrc& rc,
+                                              uint32_t wg) {
+  constexpr int NT_W = 2, KT_W = 4;
+  const short* __restrict__ AT = p.AT;
+  const int32_t N = p.N, K = p.K;
+  const int64_t mchunks = p.mchunks, nslabs = p.nslabs;
+  const int64_t chunks_per_slab = p.chunks_per_slab;
+
+  constexpr int32_t NBLK = 4;  // nblk_n = 1, nblk_k = 4
+  int64_t slab;
+  int32_t bk;
+  if (p.nblk_n < 0) {  // linear decode
+    bk = (int32_t)(wg % (uint32_t)NBLK);
+    slab = wg / (uint32_t)NBLK;
+  } else {
+    const int32_t xcd = wg & 7;
+    const int32_t g = wg >> 3;
+    bk = g % NBLK;
+    slab = (int64_t)(g / NBLK) * 8 + xcd;
+  }
+  // Both returns are workgroup-uniform and ahead of the first barrier.
+  if (slab >= nslabs) return;
+  const int64_t c0 = slab * chunks_per_slab;
+  const int64_t cend = min(c0 + chunks_per_slab, mchunks);
+  if (c0 >= cend) return;
+  const int64_t p0 = c0 >> 1;                  // first pair
+  const int64_t np = ((cend + 1) >> 1) - p0;   // pairs touched, >= 1
+
+  const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t lane = threadIdx.x & 63;
+  const int32_t nt0 = wave * NT_W;
+  const int32_t kt0 = bk * KT_W;
+
+  // This wave's a1 n-tile: its W1 fragments and bias column, kept for the
+  // whole kernel.
+  wf_bf16x8 w1[7];
+  #pragma unroll
+  for (int kc = 0; kc < 7; kc++) {
+    w1[kc] = *reinterpret_cast<const wf_bf16x8*>(
+        rc.W1s + ((int64_t)(kt0 + wave) * 7 + kc) * 512 + lane * 8);
+  }
+  const float bv = rc.b1[(kt0 + wave) * 32 + (lane & 31)];
+  const fc_f32x2 bv2 = {bv, bv};
+
+  // Loader role: x fragments min(2w, 6), min(2w + 1, 6) of the pair's x
+  // block, dz fragments 4w .. 4w + 3 of the stage ([chunk parity][n-tile]).
+  const int32_t fx0 = wave * 2 < 6 ? wave * 2 : 6;
+  const int32_t fx1 = wave * 2 + 1 < 6 ? wave * 2 + 1 : 6;
+  const short* gx0 = rc.xs + (p0 * 7 + fx0) * 512 + lane * 8;
+  const short* gx1 = rc.xs + (p0 * 7 + fx1) * 512 + lane * 8;
+  const short* gd[4];
+  #pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int32_t f = wave * 4 + j;
+    gd[j] = AT + ((int64_t)(f & 7) * mchunks + 2 * p0 + (f >> 3)) * 512 +
+            lane * 8;
+  }
+
+  wf_f32x16 acc[NT_W][KT_W] = {};
+
+#define RC_DMA(src, dst)                                                   \
+  __builtin_amdgcn_global_load_lds(                                        \
+      (const __attribute__((address_space(1))) void*)(src),                \
+      (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
+// One pair's six DMAs of this wave: x first, then dz.
+#define RC_ISSUE(ds, xsl)                                                  \
+  {                                                                        \
+    short* xb = ring + kRcXOff + (xsl) * kRcXSlotElems;                    \
+    RC_DMA(gx0, xb + fx0 * 512);                                           \
+    RC_DMA(gx1, xb + fx1 * 512);                                           \
+    gx0 += kRcXSlotElems;                                                  \
+    gx1 += kRcXSlotElems;                                                  \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {                        \
+      RC_DMA(gd[j], ring + (ds) * kRcDzStageElems + (wave * 4 + j) * 512); \
+      gd[j] += 2 * 512;                                                    \
+    }                                                                      \
+  }
+#define RC_RECOMPUTE(xsl, pb)                                              \
+  {                                                                        \
+    const short* xp = ring + kRcXOff + (xsl) * kRcXSlotElems + lane * 8;   \
+    wf_bf16x8 xa[7];                                                       \
+    _Pragma("unroll") for (int kc = 0; kc < 7; kc++) {                     \
+      xa[kc] = *reinterpret_cast<const wf_bf16x8*>(xp + kc * 512);         \
+    }                                                                      \
+    wf_f32x16 c = {};                                                      \
+    _Pragma("unroll") for (int kc = 0; kc < 7; kc++) {                     \
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[kc], w1[kc], c, 0, 0, \
+                                                  0);                      \
+    }                                                                      \
+    uint32_t pk[8];                                                        \
+    _Pragma("unroll") for (int q = 0; q < 8; q++) {                        \
+      pk[q] = fc_epi_pair<true>(c[2 * q], c[2 * q + 1], bv2);              \
+    }                                                                      \
+    fc_u32x4 run0, run1;                                                   \
+    fc_half_row_exchange(pk, lane >> 5, run0, run1);                       \
+    short* pp = ring + kRcPubOff + (pb) * kRcPubElems + wave * 512 +       \
+                lane * 8;                                                  \
+    *reinterpret_cast<fc_u32x4*>(pp) = run0;                               \
+    *reinterpret_cast<fc_u32x4*>(pp + KT_W * 512) = run1;                  \
+  }
+#define RC_CONSUME(ds, pb, par)                                            \
+  {                                                                        \
+    const short* sp =                                                      \
+        ring + (ds) * kRcDzStageElems + (par) * 8 * 512 + lane * 8;        \
+    const short* bp =                                                      \
+        ring + kRcPubOff + (pb) * kRcPubElems + (par) * KT_W * 512 +       \
+        lane * 8;                                                          \
+    wf_bf16x8 a[NT_W], b[KT_W];                                            \
+    _Pragma("unroll") for (int nt = 0; nt < NT_W; nt++) {                  \
+      a[nt] = *reinterpret_cast<const wf_bf16x8*>(sp + (nt0 + nt) * 512);  \
+    }                                                                      \
+    _Pragma("unroll") for (int kt = 0; kt < KT_W; kt++) {                  \
+      b[kt] = *reinterpret_cast<const wf_bf16x8*>(bp + kt * 512);          \
+    }                                                                      \
+    _Pragma("unroll") for (int nt = 0; nt < NT_W; nt++) {                  \
+      _Pragma("unroll") for (int kt = 0; kt < KT_W; kt++) {                \
+        acc[nt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(             \
+            a[nt], b[kt], acc[nt][kt], 0, 0, 0);                           \
+      }                                                                    \
+    }                                                                      \
+  }
+// The barrier between pairs: the asm fences keep the compiler's LDS
+// accesses on their side of it.
+#define RC_BARRIER()                                                       \
+  {                                                                        \
+    __builtin_amdgcn_s_barrier();                                          \
+    asm volatile("" ::: "memory");                                         \
+  }
+
+  // Pair j lives in dz stage j % 3, x slot j & 1, publish buffer j & 1.
+  RC_ISSUE(0, 0);
+  if (np > 1) {
+    RC_ISSUE(1, 1);
+    WL_WAIT(10);  // x of pair 0
+  } else {
+    WL_WAIT(4);
+  }
+  RC_BARRIER();
+  RC_RECOMPUTE(0, 0);
+  int32_t ds = 0;  // j % 3
+  int64_t j = 0;
+  // Steady state: pairs up to j + 1 are issued; x(j + 1) and dz(j) must
+  // have landed, the 4 dz DMAs of pair j + 1 stay outstanding.
+  for (; j + 2 < np; j++) {
+    WL_WAIT(4);
+    RC_BARRIER();
+    const int32_t pb = (int32_t)(j & 1);
+    RC_ISSUE(ds == 0 ? 2 : ds - 1, pb);  // pair j + 2: stage (j + 2) % 3
+    RC_RECOMPUTE(pb ^ 1, pb ^ 1);
+    // Only the slab's first chunk can lie below c0.
+    if (j > 0 || !(c0 & 1)) RC_CONSUME(ds, pb, 0);
+    RC_CONSUME(ds, pb, 1);  // j < np - 1: chunk 2j + 1 is inside the slab
+    ds = ds == 2 ? 0 : ds + 1;
+  }
+  // Drain: nothing left to issue.
+  for (; j < np; j++) {
+    const int32_t pb = (int32_t)(j & 1);
+    if (j + 1 < np) {
+      WL_WAIT(4);
+      RC_BARRIER();
+      RC_RECOMPUTE(pb ^ 1, pb ^ 1);
+    } else {
+      WL_WAIT(0);
+      RC_BARRIER();
+    }
+    if (j > 0 || !(c0 & 1)) RC_CONSUME(ds, pb, 0);
+    if (2 * (p0 + j) + 1 < cend) RC_CONSUME(ds, pb, 1);
+    ds = ds == 2 ? 0 : ds + 1;
+  }
+#undef RC_DMA
+#undef RC_ISSUE
+#undef RC_RECOMPUTE
+#undef RC_CONSUME
+#undef RC_BARRIER
+
+  // Epilogue: as in wgrad_frag_kernel.
+  float* part = p.part + slab * (int64_t)N * K;
+  #pragma unroll
+  for (int nt = 0; nt < NT_W; nt++) {
+    #pragma unroll
+    for (int kt = 0; kt < KT_W; kt++) {
+      const int32_t k = (kt0 + kt) * 32 + (lane & 31);
+      #pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int32_t n = (nt0 + nt) * 32 + (reg & 3) + 8 * (reg >> 2) +
+                          4 * (lane >> 5);
+        part[(int64_t)n * K + k] = acc[nt][kt][reg];
+      }
+    }
+  }
+}
 #undef WL_WAIT
 
 template <int NT_W, int KT_W>
@@ -457,25 +703,41 @@ __global__ void __launch_bounds__(256, 2) wgrad_lds_kernel(
 // partition. With all three resident at once the slab counts no longer
 // have to fill the chip per problem: 512 workgroups in all keep every
 // slot busy and the partials at 512 x 128 KB.
+// RC: the dW2 workgroups run wgrad_rc_body (a1 recomputed from g.rc; p[1].BT
+// is not read) on the same slabs and the same number of workgroups.
 struct WgradGroupedArgs {
   WgradProblem p[3];
   uint32_t start[3];  // first workgroup of each problem; start[0] == 0
+  WgradRcSrc rc;
 };
 
+constexpr int kLdsRingElems = kLdsStages * kLdsStageElems;
+
+template <bool RC>
 __global__ void __launch_bounds__(256, 2) wgrad_grouped_kernel(
     const WgradGroupedArgs g) {
   __shared__ __attribute__((aligned(16))) short
-      ring[kLdsStages * kLdsStageElems];
+      ring[RC && kRcRingElems > kLdsRingElems ? kRcRingElems
+                                              : kLdsRingElems];
   // Workgroup-uniform problem select, ahead of every barrier and every
   // vector-memory operation.
   const uint32_t b = blockIdx.x;
   if (b < g.start[1]) {
     wgrad_lds_body<2, 4>(ring, g.p[0], b);
+  } else if (RC && b < g.start[2]) {
+    wgrad_rc_body(ring, g.p[1], g.rc, b - g.start[1]);
   } else {
-    const bool dw2 = b < g.start[2];
+    const bool dw2 = !RC && b < g.start[2];
     wgrad_lds_body<1, 8>(ring, dw2 ? g.p[1] : g.p[2],
                          b - (dw2 ? g.start[1] : g.start[2]));
   }
+}
+
+// The recompute body alone, on the dW2 slabs of the grouped launch.
+__global__ void __launch_bounds__(256, 2) wgrad_rc_kernel(
+    const WgradProblem p, const WgradRcSrc rc) {
+  __shared__ __attribute__((aligned(16))) short ring[kRcRingElems];
+  wgrad_rc_body(ring, p, rc, blockIdx.x);
 }
 
 // out[i] = sum_s part[s][i] — the slab-partial reduction (fp32, float4).
@@ -790,8 +1052,10 @@ WgradGroupedSlabs launch_wgrad_grouped(const void* AT1, const void* BT1,
                                        const void* BT2, float* part2,
                                        const void* AT3, const void* BT3,
                                        float* part3, int64_t mchunks,
+                                       const WgradRecompute* rc,
                                        hipStream_t stream) {
-  // dW1 [512,128] <2,4>; dW2 [256,512] <1,8>; dW3 [128,256] <1,8>
+  // dW1 [512,128] <2,4>; dW2 [256,512] <1,8>; dW3 [128,256] <1,8>. With
+  // ``rc`` dW2 runs the recompute body, <2,4>: as many blocks per slab.
   static const int32_t shp[3][4] = {
       {512, 128, 2, 4}, {256, 512, 1, 8}, {128, 256, 1, 8}};
   const void* at[3] = {AT1, AT2, AT3};
@@ -817,9 +1081,58 @@ WgradGroupedSlabs launch_wgrad_grouped(const void* AT1, const void* BT1,
     // slab count rounded up to the 8 XCDs: the surplus workgroups return
     grid += (uint32_t)(((p.nslabs + 7) / 8) * 8 * p.nblk_n * p.nblk_k);
   }
-  hipLaunchKernelGGL(wgrad_grouped_kernel, dim3(grid), dim3(256), 0, stream,
-                     g);
+  if (rc != nullptr) {
+    g.p[1].BT = nullptr;
+    g.p[1].nblk_n = 1;
+    g.p[1].nblk_k = 4;
+    g.rc = {reinterpret_cast<const short*>(rc->xs),
+            reinterpret_cast<const short*>(rc->W1s), rc->b1};
+    hipLaunchKernelGGL(wgrad_grouped_kernel<true>, dim3(grid), dim3(256), 0,
+                       stream, g);
+  } else {
+    hipLaunchKernelGGL(wgrad_grouped_kernel<false>, dim3(grid), dim3(256), 0,
+                       stream, g);
+  }
   return r;
+}
+
+// Whether fused_step_bf16 pairs the forward without a1^T with the
+// recompute body where it can (grouped launch, 64-row slabs, no pi16):
+// RSDL_WGRAD_RECOMPUTE (0 or 1, read once) if set, else this default.
+#ifndef RSDL_WGRAD_RECOMPUTE_DEFAULT
+#define RSDL_WGRAD_RECOMPUTE_DEFAULT 1
+#endif
+
+bool wgrad_recompute_default() {
+  static const bool on = [] {
+    const char* e = std::getenv("RSDL_WGRAD_RECOMPUTE");
+    if (e != nullptr && (e[0] == '0' || e[0] == '1') && e[1] == '\0') {
+      return e[0] == '1';
+    }
+    return RSDL_WGRAD_RECOMPUTE_DEFAULT != 0;
+  }();
+  return on;
+}
+
+int64_t launch_wgrad_recompute(const WgradRecompute& rc, const void* AT2,
+                               float* part2, int64_t mchunks,
+                               hipStream_t stream) {
+  WgradProblem p{};
+  p.AT = reinterpret_cast<const short*>(AT2);
+  p.part = part2;
+  p.N = 256;
+  p.K = 512;
+  p.mchunks = mchunks;
+  p.nblk_n = 1;
+  p.nblk_k = 4;
+  grouped_slabs(grouped_targets()[1], mchunks, &p.nslabs,
+                &p.chunks_per_slab);
+  const WgradRcSrc src{reinterpret_cast<const short*>(rc.xs),
+                       reinterpret_cast<const short*>(rc.W1s), rc.b1};
+  const uint32_t grid = (uint32_t)(((p.nslabs + 7) / 8) * 8 * 4);
+  hipLaunchKernelGGL(wgrad_rc_kernel, dim3(grid), dim3(256), 0, stream, p,
+                     src);
+  return p.nslabs;
 }
 
 }  // namespace rsdl

@@ -9,11 +9,14 @@ and no copy:
   2. x swizzle (emits both x layouts)
   3. fwd chain (3 MFMA layers + head + loss/grad, MSE or binary
      cross-entropy with logits, optionally with per-row sample weights
-     and a positive-class weight; emits a1^T/a2^T wgrad fragments +
-     relu-mask words)
+     and a positive-class weight; emits the a2^T wgrad fragments +
+     relu-mask words, and a1^T only where the dW2 wgrad does not
+     recompute a1: see _WGRAD_RECOMPUTE)
   4. bwd chain (dgrad chain from mask bits; emits dz^T fragments + db/dW4
      partials)
-  5-7. three fragment-major wgrad kernels into per-slab partials
+  5-7. three fragment-major wgrad kernels into per-slab partials (one
+     grouped launch by default, whose dW2 workgroups recompute a1 from
+     the fragment-major x and W1 in place of reading a1^T)
   8. step_finalize: all partials -> dW1 [512,100], dW2, dW3, dW4, db1..4
      and the scalar loss, fixed summation order, written in place
 then the optimizer. With ``optimizer=`` (models/fused_optim.py, SGD or
@@ -78,6 +81,16 @@ _WGRAD_VARIANT = 0
 # partition of the fp32 sums of dW1-dW3 differs. Tests may override via
 # fused_step._WGRAD_GROUPED.
 _WGRAD_GROUPED = None
+
+# Whether hip.fused_step_bf16 keeps a1^T out of HBM: the forward chain then
+# emits no a1^T (it is never allocated) and the dW2 workgroups of the
+# grouped launch recompute a1 = relu(x W1^T + b1) from the fragment-major x
+# and W1 (csrc/wgrad_frag.hip, wgrad_rc_body). None = the extension's
+# default (its RSDL_WGRAD_RECOMPUTE latch, then the build's default), True /
+# False = on / off for this process. It applies with the grouped launch,
+# 64-row slabs and no pi16 only, and every result is bit-identical either
+# way. Tests may override via fused_step._WGRAD_RECOMPUTE.
+_WGRAD_RECOMPUTE = None
 
 # Native glue (default on; RSDL_NATIVE_GLUE=0 or fused_step._NATIVE_GLUE =
 # False forces the composed path): the whole schedule runs inside one
@@ -226,11 +239,13 @@ def _rows_kw() -> dict:
 
 
 def _wgrad_kw() -> dict:
-    """``wgrad_variant=`` / ``wgrad_grouped=`` for hip.fused_step_bf16;
-    empty at the defaults, as _rows_kw is."""
+    """``wgrad_variant=`` / ``wgrad_grouped=`` / ``wgrad_recompute=`` for
+    hip.fused_step_bf16; empty at the defaults, as _rows_kw is."""
     kw = {"wgrad_variant": _WGRAD_VARIANT} if _WGRAD_VARIANT else {}
     if _WGRAD_GROUPED is not None:
         kw["wgrad_grouped"] = int(bool(_WGRAD_GROUPED))
+    if _WGRAD_RECOMPUTE is not None:
+        kw["wgrad_recompute"] = int(bool(_WGRAD_RECOMPUTE))
     return kw
 
 

@@ -12,7 +12,13 @@ times the larger within-variant spread. One JSON line per shape.
 
 ``--grouped [ROUNDS]`` times the step's three wgrad launches against the
 one grouped launch that replaces them (wgrad_grouped_kernel), alternated
-the same way; RSDL_WGRAD_GROUP_SLABS picks the split under test."""
+the same way; RSDL_WGRAD_GROUP_SLABS picks the split under test.
+
+``--recompute [ROUNDS]`` times the dW2 wgrad alone, reading a1^T (the ring
+kernel, as the step ran it before the recompute body) against recomputing
+a1 from the fragment-major x and W1 (wgrad_rc_kernel), alternated the same
+way. The recompute arm reads 200 MB less at M = 250k; the forward's saving
+(no a1^T stores) is not part of this figure."""
 import argparse
 import json
 import os
@@ -146,11 +152,61 @@ def grouped(M, rounds):
     }), flush=True)
 
 
+def recompute(M, rounds):
+    """dW2 alone (raw partials): a1^T read from HBM by the ring kernel
+    against a1 recomputed in the kernel; the rule of ``ab``. One JSON line."""
+    hip = _load_hip()
+    mchunks = 2 * ((M + 31) // 32)
+    dz2t, a1t = inputs(256, 512, mchunks)
+    xs = torch.randn(mchunks // 2 * 7 * 512, device="cuda").bfloat16()
+    w1s = (0.1 * torch.randn(512 * 112, device="cuda")).bfloat16()
+    b1 = torch.randn(512, device="cuda")
+
+    def read():
+        return hip.wgrad_frag_partials_bf16(dz2t, a1t, 256, 512, mchunks, 1,
+                                            8, variant=2)
+
+    def rc():
+        return hip.wgrad_recompute_partials_bf16(xs, w1s, b1, dz2t, mchunks)
+
+    arms = {"read": read, "recompute": rc}
+    us = {k: [] for k in arms}
+    slabs = {k: fn().shape[0] for k, fn in arms.items()}
+    for r in range(-1, rounds):  # round -1: discarded warm-up pair
+        for k, fn in arms.items():
+            us_k = t(fn) * 1e3
+            if r >= 0:
+                us[k].append(us_k)
+    by = {"read": (dz2t.numel() + a1t.numel()) * 2,
+          "recompute": (dz2t.numel() + xs.numel()) * 2}
+    by = {k: v + slabs[k] * 256 * 512 * 4 for k, v in by.items()}
+    med = {k: statistics.median(us[k]) for k in us}
+    spread = max(max(us[k]) - min(us[k]) for k in us)
+    diff = med["read"] - med["recompute"]
+    passes = max(us["recompute"]) < min(us["read"]) and diff >= 3 * spread
+    print(json.dumps({
+        "M": M, "slabs": slabs,
+        "read_us": [round(x, 2) for x in us["read"]],
+        "recompute_us": [round(x, 2) for x in us["recompute"]],
+        "read_med_us": round(med["read"], 2),
+        "recompute_med_us": round(med["recompute"], 2),
+        "read_bytes_MB": round(by["read"] / 1e6, 1),
+        "recompute_bytes_MB": round(by["recompute"] / 1e6, 1),
+        "read_TBps": round(by["read"] / med["read"] / 1e6, 2),
+        "recompute_TBps": round(by["recompute"] / med["recompute"] / 1e6, 2),
+        "median_diff_us": round(diff, 2),
+        "max_spread_us": round(spread, 2),
+        "recompute_passes_rule": passes,
+    }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--ab", type=int, nargs="?", const=5, default=0,
                    metavar="ROUNDS")
     p.add_argument("--grouped", type=int, nargs="?", const=7, default=0,
+                   metavar="ROUNDS")
+    p.add_argument("--recompute", type=int, nargs="?", const=7, default=0,
                    metavar="ROUNDS")
     p.add_argument("--rows", type=int, default=250_000)
     args = p.parse_args()
@@ -160,6 +216,9 @@ def main():
         return
     if args.grouped:
         grouped(M, args.grouped)
+        return
+    if args.recompute:
+        recompute(M, args.recompute)
         return
     mchunks = 2 * ((M + 31) // 32)
     print(f"RSDL_WGRAD_SCHED={os.environ.get('RSDL_WGRAD_SCHED', '0')}")
